@@ -7,7 +7,9 @@ Default workload = BASELINE.json configs[1]: Cornell box 512x512, `integrator=dr
 before the timed region. Metric = mutations/s (accepted + rejected; one mutation = one first-stage proposal,
 reference drmlt_proc.cpp:541).
 
-  python bench.py --gpus 1 --steps 10 --warmup 2      # the defaults
+  python bench.py --gpus 1 --steps 10 --warmup 2      # the defaults: set up, warm up, time the steps, print the line
+  python bench.py --full                              # + image quality against a device path-traced reference, CPU baseline
+  python bench.py --dump-outputs DIR                  # + what the timed render computed, as DIR/<name>.npy
   python bench.py --config 3|5|bdpt|soup|soup50k  # the other kernels, same JSON line (roofline of THAT kernel)
   python bench.py --gpus N --steps K --warmup W       # N > 1, no launcher: ONE process drives the N devices (drmlt_node_*)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -141,6 +143,21 @@ def _clean(o):
     return o
 
 
+def dump_outputs(out_dir, arrays, budget=64 << 20):
+    """DIR/<name>.npy, float32 or float64. An array larger than half the budget is stored as a fixed, seeded sample of its rows (pixels
+    of an image): <name>.npy holds the sampled rows, <name>_index.npy their flat indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > budget // 2:
+            rows = a.reshape(-1, a.shape[-1] if a.ndim > 1 else 1)
+            n = (budget // 2) // (rows.shape[1] * a.itemsize + 8)
+            idx = np.sort(np.random.default_rng(0x5EED).choice(rows.shape[0], size=n, replace=False))
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            a = rows[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def lum(img):
     return img @ np.array([0.212671, 0.715160, 0.072169])
 
@@ -193,8 +210,12 @@ def main():
     ap.add_argument("--chains", type=int, default=None, help="chains per GPU (default: the configuration's own, 65536 unless noted)")
     ap.add_argument("--spp", type=int, default=0, help="mutations per pixel per step (sampleCount)")
     ap.add_argument("--type", default="")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-quality", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: image quality against a "
+                    "device path-traced reference (technique=path) and the CPU baseline (world size 1); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps, write what they computed as DIR/<name>.npy: "
+                    "the developed image, the luminance normalisation b and the timed steps' mutation counts")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-quality", action="store_true", help="with --full: leave out the image quality")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--with-progress", action="store_true", help="run with a progress callback, as the Mitsuba plugin does: the library then cuts "
                     "the call into launches of 256 mutations per chain and synchronises after each (ADVICE r03: the plugin path's own line)")
@@ -382,6 +403,25 @@ def main():
     rays = st1.rays - st0.rays
     value = world * args.steps * step_mutations / elapsed
 
+    if args.dump_outputs:
+        # what the timed render computed, as its caller receives it (outside the timed region): the developed image -- the node's
+        # stitched one; one process per GPU: every rank's tile, gathered on rank 0 --, b and the timed steps' mutation counts (mutations,
+        # accepted: this process's, the node's sums in node mode)
+        if node_mode:
+            img_out = img_node
+        elif use_dist:
+            tile, rows, _ = ctx.exchange_tiled(b)
+            parts = [None] * world
+            dist.all_gather_object(parts, (rows, tile))
+            img_out = np.zeros((res, res, 3), dtype=np.float32)
+            for (lo, hi), t in parts:
+                img_out[lo:hi] = t
+        else:
+            img_out = ctx.develop()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"image": img_out, "b": np.array([b], dtype=np.float64),
+                                             "mutations": np.array([muts, accepted], dtype=np.float64)})
+
     out = None
     if rank == 0:
         # ---- roofline of the dominant kernel: algorithmic bytes per SURVEY 8(d) / DESIGN.md section 3
@@ -513,10 +553,10 @@ def main():
             except Exception:
                 pass
 
-    # ---- image quality at the accumulated budget (outside the timed region)
+    # ---- --full: image quality at the accumulated budget (outside the timed region)
     # (technique=path only: the device path tracer used as reference shares the path integrator's treatment of maxDepth;
     # the bidirectional techniques are held to the oracle's bdpt / mmlt renders in tests/test_gpu_bdpt.py, test_gpu_mmlt.py)
-    if not args.no_quality and not conf.get("no_quality") and not cfg_kw.get("acceptance_map") and cfg_kw.get("technique", "path") == "path":
+    if args.full and not args.no_quality and not conf.get("no_quality") and not cfg_kw.get("acceptance_map") and cfg_kw.get("technique", "path") == "path":
         if use_dist:  # every rank develops its tile of the summed film; rank 0 collects them
             tile, rows, b_mean = ctx.exchange_tiled(b)
             parts = [None] * world
@@ -556,12 +596,14 @@ def main():
                 out["quality"]["at_budget"] = {"mutations_per_pixel": goal_mpp,
                                                "rel_mse": float(np.mean((lum(img2) - lr) ** 2 / (lr ** 2 + eps))),
                                                "meets_1e-3": bool(np.mean((lum(img2) - lr) ** 2 / (lr ** 2 + eps)) < 1e-3)}
-    if rank == 0 and world == 1 and conf.get("no_cpu_baseline"):
-        out["cpu_baseline"] = {"value": None, "unit": "mutations/s", "cores": 0, "kind": "port", "sample": "not measured: " + conf["no_cpu_baseline"]}
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(pkg, conf, res, cfg_kw, args.cpu_seconds)
-    elif rank == 0:
-        out["cpu_baseline"] = None
+    # ---- --full: the CPU baseline
+    if args.full:
+        if rank == 0 and world == 1 and conf.get("no_cpu_baseline"):
+            out["cpu_baseline"] = {"value": None, "unit": "mutations/s", "cores": 0, "kind": "port", "sample": "not measured: " + conf["no_cpu_baseline"]}
+        elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(pkg, conf, res, cfg_kw, args.cpu_seconds)
+        elif rank == 0:
+            out["cpu_baseline"] = None
     if rank == 0:
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)

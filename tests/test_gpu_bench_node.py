@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -52,3 +53,30 @@ def test_single_gpu_line_keeps_its_shape(native_lib):
     assert out["n_gpus"] == 1 and out["launch_mode"] == "single" and out["rccl_nranks"] is None and out["selfcheck"] is None
     for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in out
+
+
+def test_plain_line_measures_the_headline_and_dumps_what_it_computed(native_lib, tmp_path):
+    """A plain run leaves the image quality and the CPU baseline to --full; --dump-outputs writes what the timed render computed:
+    its developed image (normalised to b), b and the timed steps' mutation counts."""
+    d = tmp_path / "out"
+    p = _bench(["--gpus", "1", "--dump-outputs", str(d)] + SMALL, {})
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    assert "quality" not in out and "cpu_baseline" not in out
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert sorted(os.listdir(d)) == ["b.npy", "image.npy", "mutations.npy"]
+    img, b, muts = np.load(d / "image.npy"), np.load(d / "b.npy"), np.load(d / "mutations.npy")
+    assert img.shape == (128, 128, 3) and img.dtype == np.float32 and np.isfinite(img).all()
+    assert b.dtype == np.float64 and b.shape == (1,) and b[0] > 0
+    assert muts.dtype == np.float64 and muts[0] == 2 * 128 * 128 * 64 and 0 < muts[1] < muts[0]
+    mean_lum = float((img.astype(np.float64) @ np.array([0.212671, 0.715160, 0.072169])).mean())
+    assert abs(mean_lum - b[0]) <= 1e-3 * b[0]
+
+
+def test_full_line_adds_quality_and_cpu_baseline(native_lib):
+    p = _bench(["--gpus", "1", "--full", "--cpu-seconds", "0.5"] + [a for a in SMALL if a != "--no-cpu-baseline"],
+               {"BENCH_REF_SPP": "256", "BENCH_QUALITY_MPP": "0"})
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    assert out["quality"]["rel_mse"] >= 0 and out["quality"]["mutations_per_pixel"] == 2 * 64
+    assert out["cpu_baseline"]["value"] > 0 and out["cpu_baseline"]["kind"] == "port"
