@@ -54,10 +54,11 @@ DEV float gaussian_sample(float u1, float u2, float sigma) {
     return tmp * cos_rev(u2) * sigma;
 }
 // log pdf of the (unscaled) Kelemen kernel, transition.h:113-122
+// (a select, not an early return: in an unrolled ratio loop every return was an exec mask kept in scalar registers)
 DEV float kelemen_logpdf(float du) {
     float d = fabsf(du);
-    if (d < KELEMEN_S1 || d > KELEMEN_S2) return -INFINITY;
-    return -__logf(2.f * d * 2.772588722239781f); // ln(s2/s1) = ln 16
+    const float l = -__logf(2.f * d * 2.772588722239781f); // ln(s2/s1) = ln 16
+    return (d < KELEMEN_S1 || d > KELEMEN_S2) ? -INFINITY : l;
 }
 
 // STRIDE: floats per row of the chain-state rows in LDS (x[k] of the chain in column `lane` = lds_x[k * STRIDE + lane])
@@ -1448,6 +1449,124 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
     ps.has_bounce = true;
     ps.phase = PH_CLOSEST;
     ps.nrays++;
+}
+
+// path_step<true, 0, SamplerT, TablesT, false> without its control flow: scenes of diffuse polygons only, two lanes per chain,
+// paths begun by the caller (k_mutate_v4). Every lane computes the hit's vertex, the emitter-hit MIS term, the roulette
+// decision, the light sample and the bounce once, in one instruction stream; the step's outcome (phase, dimensions used,
+// radiance, rays) is then selected. The operations and their order are those of path_step, so f(u) is bit for bit the
+// same. A lane whose path ends may compute garbage (NaN, inf) in what it does not use; none of it reaches `ps` or `sr`:
+// radiance, dimensions and rays are selected, the shadow ray is written only when it is handed over, and the vertex
+// and bounce fields only when the path goes on (a path that ends, or waits for its shadow ray, never reads them again).
+template <class SamplerT, class TablesT>
+DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, SamplerT &smp, const Hit &hit, bool shadow_clear,
+                           ShadowRay &sr) {
+    static_assert(draws_batched<SamplerT>::value, "the five draws are requested together");
+    const uint32_t kmax = (uint32_t) P.eff_dim - 1u, k0 = ps.k;
+    const float v0 = smp.next(min(k0, kmax)), v1 = smp.next(min(k0 + 1u, kmax)), v2 = smp.next(min(k0 + 2u, kmax));
+    const float v3 = smp.next(min(k0 + 3u, kmax)), v4 = smp.next(min(k0 + 4u, kmax));
+    sr.valid = false;
+    // the partner's verdict on the previous vertex's shadow ray
+    f3 Li = ps.Li;
+    if (ps.shadow_pending && shadow_clear) Li = Li + ps.nee;
+    // live: a PH_CLOSEST step whose ray hit something (PH_FLUSH and misses end the path here)
+    const bool live = ps.phase != PH_FLUSH && hit.prim >= 0;
+    const DShade S = T.shade(hit.prim >= 0 ? hit.prim : 0);
+    const f3 p = fma3(ld3(S.eu), hit.u, fma3(ld3(S.ev), hit.v, ld3(S.origin)));
+    const f3 n = ld3(S.n);
+    const f3 s = ld3(S.eu) * S.inv_len_eu;
+    const bool hb = ps.has_bounce;
+    const f3 thr_b = hb ? ps.thr * ps.bweight : ps.thr;
+    const float eta = hb ? ps.eta * ps.beta_eta : ps.eta;
+    // emitter hit by the BSDF-sampled ray: MIS against direct sampling (refN is never zeroed without dielectrics)
+    {
+        const DEmitter E = T.emitter(S.emitter >= 0 ? S.emitter : 0);
+        const float dn = dot3(ps.d, n);
+        const float dr = dot3(ps.d, ps.n);
+        float lumPdf = S.inv_area * hit.t * hit.t / fabsf(dn);
+        lumPdf *= E.cdf_hi - E.cdf_lo;
+        lumPdf = (!ps.bdelta && dr >= 0.f) ? lumPdf : 0.f;
+        const float a = ps.bpdf * ps.bpdf, b = lumPdf * lumPdf;
+        const f3 Lm = fma3(thr_b * ld3(E.radiance), a / (a + b), Li);
+        if (live && hb && S.emitter >= 0 && ps.direct_on && ps.non_specular && dn < 0.f) Li = Lm;
+    }
+    const bool want_rr = hb && ps.depth >= P.rr_depth;
+    const int depth = hb ? ps.depth + 1 : ps.depth;
+    const bool direct_on = hb || ps.direct_on;
+    const bool at_max = depth >= P.max_depth && P.max_depth > 0;
+    const float rr_q = fminf(max3(thr_b) * eta * eta, 0.95f);
+    const bool survives = !want_rr || !(v0 >= rr_q);
+    const f3 thr = want_rr ? thr_b * (1.f / rr_q) : thr_b;
+    // go: the vertex is adopted and samples a light and a bounce
+    const bool go = live && !at_max && survives;
+    const f3 t = cross3(n, s);
+    const f3 md = -ps.d;
+    const f3 wi = mk3(dot3(md, s), dot3(md, t), dot3(md, n));
+    const int bsdf = S.bsdf & 0xffffff;
+    const DBsdf B = T.bsdf(bsdf);
+    const bool want_nee = direct_on && B.type == 0;
+    const float sx0 = want_rr ? v1 : v0, sy = want_rr ? v2 : v1;
+    const int bpos = (want_rr ? 1 : 0) + (want_nee ? 2 : 0);
+    const float bx = bpos == 0 ? v0 : (bpos == 1 ? v1 : (bpos == 2 ? v2 : v3));
+    const float by = bpos == 0 ? v1 : (bpos == 1 ? v2 : (bpos == 2 ? v3 : v4));
+    // direct illumination sampling
+    int ei = 0; // DiscreteDistribution::sample (lower_bound semantics); the loop is wave-uniform
+    for (int i = 1; i < P.n_emitters; ++i)
+        if (T.emitter_cdf_lo(i) < sx0) ei = i;
+    const DEmitter E = T.emitter(ei);
+    const float emPdf = E.cdf_hi - E.cdf_lo;
+    const float sx = (sx0 - E.cdf_lo) / emPdf; // sampleReuse
+    const DShade L = T.emitter_shade(ei, E);
+    f3 lp;
+    if ((L.bsdf >> 24) == PRIM_RECTANGLE) lp = fma3(ld3(L.eu), sx, fma3(ld3(L.ev), sy, ld3(L.origin)));
+    else { const float a = sqrtf(fmaxf(0.f, 1.f - sx)); lp = fma3(ld3(L.eu), 1.f - a, fma3(ld3(L.ev), a * sy, ld3(L.origin))); }
+    const f3 ln = ld3(L.n);
+    const f3 dv = lp - p;
+    const float dist2 = dot3(dv, dv), dist = sqrtf(dist2);
+    const f3 dd = dv * (1.f / dist);
+    const float dln = dot3(dd, ln);
+    const float pdf = dln != 0.f ? L.inv_area * dist2 / fabsf(dln) : 0.f;
+    const float drl = dot3(dd, n);
+    const f3 wo_l = mk3(dot3(dd, s), dot3(dd, t), dot3(dd, n));
+    const f3 bsdfVal = ld3(B.rgb) * (INV_PI_F * wo_l.z);
+    const float bsdfPdf = INV_PI_F * wo_l.z;
+    const float lpdf = pdf * emPdf;
+    const float a = lpdf * lpdf, b = bsdfPdf * bsdfPdf;
+    const f3 value = ld3(E.radiance) * (1.f / lpdf);
+    const f3 c = thr * value * bsdfVal * (a / (a + b));
+    const bool nee = go && want_nee && drl >= 0.f && dln < 0.f && pdf != 0.f && wi.z > 0.f && wo_l.z > 0.f && !is_zero3(c);
+    // BSDF sampling (diffuse.cpp:139-149)
+    const f3 wo = square_to_cosine_hemisphere(bx, by);
+    const f3 bweight = ld3(B.rgb);
+    const bool bounce = go && B.type == 0 && wi.z > 0.f && !is_zero3(bweight);
+    // outcome
+    ps.Li = Li;
+    ps.k = k0 + ((live && want_rr) ? 1u : 0u) + (go ? (want_nee ? 4u : 2u) : 0u);
+    ps.nrays += (nee ? 1u : 0u) + (bounce ? 1u : 0u);
+    ps.shadow_pending = nee;
+    ps.phase = bounce ? PH_CLOSEST : (nee ? PH_FLUSH : PH_DONE);
+    if (nee) {
+        ps.nee = c;
+        sr.o = p; sr.d = dd;
+        sr.tmin = ray_eps_shadow(p);
+        sr.tmax = dist * (1.f - SHADOW_EPSILON_F);
+        sr.valid = true;
+    }
+    if (bounce) {
+        ps.thr = thr; ps.eta = eta; ps.depth = depth; ps.direct_on = direct_on;
+        ps.wi = wi;
+        ps.o = p; ps.n = n; ps.s = s;
+        ps.bsdf = bsdf;
+        ps.bpdf = INV_PI_F * wo.z;
+        ps.bweight = bweight;
+        ps.beta_eta = 1.f;
+        ps.bdelta = false;
+        ps.non_specular = true;
+        ps.d = fma3(s, wo.x, fma3(t, wo.y, n * wo.z));
+        ps.tmin = ray_eps_closest(p);
+        ps.tmax = INFINITY;
+        ps.has_bounce = true;
+    }
 }
 
 // PSSMLTSampler (src/integrators/pssmlt/pssmlt_sampler.cpp:93-168, pssmlt_sampler.h:113-143) as a pure function of the

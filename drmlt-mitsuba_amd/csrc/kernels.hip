@@ -160,6 +160,8 @@ struct MhOutcome {
 template <class SamplerT> DEV float mira_ratio(SamplerT &smp, uint32_t nd1, uint32_t nd2) {
     const uint32_t dimStage = max(nd1, nd2) - 1u;
     float num = 0.f, den = 0.f;
+    // (not unrolled: the unrolled copies' compare masks were live at once and spilled scalar registers in every chain kernel)
+#pragma nounroll
     for (uint32_t i = 0; i < dimStage; ++i) {
         const float yi = smp.y_raw(i);
         num += kelemen_logpdf(smp.z_raw(i) - yi);
@@ -795,7 +797,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                     const V4Layout Y = v4_layout(Ps, QCAP);
                     RowSampler smp = Y.smp;
                     smp.lane = sub; smp.mode = smp_mode;
-                    if (LDS_TABLES) path_step<true, FEAT, RowSampler, LdsTables, false>(Ps, Y.LT, ps, smp, h, occluded == 0u, sr);
+                    if constexpr (FEAT == 0 && LDS_TABLES) path_step_diffuse(Ps, Y.LT, ps, smp, h, occluded == 0u, sr); // diffuse polygons: straight-line step
+                    else if (LDS_TABLES) path_step<true, FEAT, RowSampler, LdsTables, false>(Ps, Y.LT, ps, smp, h, occluded == 0u, sr);
                     else path_step<true, FEAT, RowSampler, GlobalTables, false>(Ps, GlobalTables{Ps.shade, Ps.bsdfs, Ps.emitters}, ps, smp, h, occluded == 0u, sr);
                 }
             }
@@ -860,33 +863,36 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
         t_mh += s1 - s0; t_trace += s2 - s1; t_step += s3 - s2; n_iter++;
     }
 #undef STAMP
+    // the epilogue reads its own copy of the block too: otherwise the compiler keeps the pointers it shares with the prologue
+    // (state rows, film, counters) in scalar registers -- spilled -- all through the loop
+    SECTION_PARAMS(Pe);
 #undef SECTION_PARAMS
     // "Perform the last splat": the current states with what they have accumulated since they were adopted
-    const V4Layout Y = v4_layout(P, QCAP);
+    const V4Layout Y = v4_layout(Pe, QCAP);
     v4_enqueue(Y.L, qn, live && cum > 0.f, cs.cur.px, cs.cur.py, cs.cur.r * cum, cs.cur.g * cum, cs.cur.b * cum);
-    v4_flush(P, Y.L, qn, lane);
+    v4_flush(Pe, Y.L, qn, lane);
     if (stamps && lane == 0) {
-        atomicAdd(P.stats + 16, t_mh); atomicAdd(P.stats + 17, t_trace); atomicAdd(P.stats + 18, t_step);
-        atomicAdd(P.stats + 19, n_iter); atomicAdd(P.stats + 20, n_mh); atomicAdd(P.stats + 21, n_busy);
-        for (int q = 0; q < 6; ++q) atomicAdd(P.stats + 26 + q, hist[q]);
-        atomicAdd(P.stats + 22, t_decide); atomicAdd(P.stats + 23, t_commit); atomicAdd(P.stats + 24, t_start); atomicAdd(P.stats + 25, t_fill);
+        atomicAdd(Pe.stats + 16, t_mh); atomicAdd(Pe.stats + 17, t_trace); atomicAdd(Pe.stats + 18, t_step);
+        atomicAdd(Pe.stats + 19, n_iter); atomicAdd(Pe.stats + 20, n_mh); atomicAdd(Pe.stats + 21, n_busy);
+        for (int q = 0; q < 6; ++q) atomicAdd(Pe.stats + 26 + q, hist[q]);
+        atomicAdd(Pe.stats + 22, t_decide); atomicAdd(Pe.stats + 23, t_commit); atomicAdd(Pe.stats + 24, t_start); atomicAdd(Pe.stats + 25, t_fill);
     }
 
     if (live) {
-        for (uint32_t k = 0; k < Y.D; ++k) P.x[(size_t) k * P.n_chains + c] = lds_x[k * S + sub];
-        P.cur_lum[c] = cs.cur.lum; P.cur_px[c] = cs.cur.px; P.cur_py[c] = cs.cur.py;
-        P.cur_r[c] = cs.cur.r; P.cur_g[c] = cs.cur.g; P.cur_b[c] = cs.cur.b;
-        if (P.chain_done) P.chain_done[c] = base + cs.it;
+        for (uint32_t k = 0; k < Y.D; ++k) Pe.x[(size_t) k * Pe.n_chains + c] = lds_x[k * S + sub];
+        Pe.cur_lum[c] = cs.cur.lum; Pe.cur_px[c] = cs.cur.px; Pe.cur_py[c] = cs.cur.py;
+        Pe.cur_r[c] = cs.cur.r; Pe.cur_g[c] = cs.cur.g; Pe.cur_b[c] = cs.cur.b;
+        if (Pe.chain_done) Pe.chain_done[c] = base + cs.it;
     }
-    if (P.chain_done && !reported && lane == 0) atomicSub(P.waves_left, 1u); // (a wave none of whose chains had anything to do)
-    flush_counters(P, ct, lane);
+    if (Pe.chain_done && !reported && lane == 0) atomicSub(Pe.waves_left, 1u); // (a wave none of whose chains had anything to do)
+    flush_counters(Pe, ct, lane);
     const unsigned long long decided = wave_sum((live && !helper) ? cs.it : 0u); // mutations decided in this launch (with run-ahead: not n_mut per chain)
-    if (lane == 0) atomicAdd(P.stats + 9, decided);
+    if (lane == 0) atomicAdd(Pe.stats + 9, decided);
     if (RESUMABLE) {
         const unsigned long long nn = wave_sum(T.n_nodes), np = wave_sum(T.n_prims);
-        if (lane == 0) { atomicAdd(P.stats + 10, nn); atomicAdd(P.stats + 11, np); atomicAdd(P.stats + 12, (unsigned long long) T.it_inner); atomicAdd(P.stats + 13, (unsigned long long) T.it_leaf); }
-        if ((P.debug & 1024) && lane == 0)
-            for (int q = 0; q < 6; ++q) atomicAdd(P.stats + 20 + q, dg[q]);
+        if (lane == 0) { atomicAdd(Pe.stats + 10, nn); atomicAdd(Pe.stats + 11, np); atomicAdd(Pe.stats + 12, (unsigned long long) T.it_inner); atomicAdd(Pe.stats + 13, (unsigned long long) T.it_leaf); }
+        if ((Pe.debug & 1024) && lane == 0)
+            for (int q = 0; q < 6; ++q) atomicAdd(Pe.stats + 20 + q, dg[q]);
     }
 }
 
