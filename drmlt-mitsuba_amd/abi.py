@@ -6,7 +6,7 @@ TYPE_GREEN, TYPE_MIRA, TYPE_ORBITAL = 0, 1, 2
 ALGO_DRMLT, ALGO_PSSMLT = 0, 1
 SHAPE_TRIANGLE, SHAPE_RECTANGLE, SHAPE_SPHERE = 0, 1, 2
 BSDF_DIFFUSE, BSDF_DIELECTRIC, BSDF_ROUGHCONDUCTOR, BSDF_CONDUCTOR = 0, 1, 2, 3
-EMITTER_AREA = 0
+EMITTER_AREA, EMITTER_POINT = 0, 1   # src/emitters/area.cpp, src/emitters/point.cpp (technique=path only)
 FILTER_BOX, FILTER_GAUSSIAN = 0, 1
 SEED_TARGET, SEED_REFERENCE = 0, 1            # drmlt_config.seed_rule (two-stage MLT seeding)
 WORK_UNITS_DEVICE, WORK_UNITS_REFERENCE = 0, 1  # drmlt_config.work_units_rule (what workUnits = -1 derives)
@@ -57,7 +57,12 @@ class Camera(C.Structure):
 class Scene(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_shapes", C.c_int32), ("n_bsdfs", C.c_int32),
                 ("n_emitters", C.c_int32), ("shapes", C.POINTER(Shape)), ("bsdfs", C.POINTER(Bsdf)),
-                ("emitters", C.POINTER(Emitter)), ("camera", Camera)]
+                ("emitters", C.POINTER(Emitter)), ("camera", Camera),
+                ("n_points", C.c_int32), ("points", C.POINTER(C.c_float))]
+
+
+# struct_size of a drmlt_scene that ends at `camera` (no point lights): include/drmlt_abi.h, DRMLT_SCENE_SIZE_NO_POINTS
+SCENE_SIZE_NO_POINTS = (Scene.camera.offset + C.sizeof(Camera) + C.sizeof(C.c_void_p) - 1) // C.sizeof(C.c_void_p) * C.sizeof(C.c_void_p)
 
 
 class Stats(C.Structure):

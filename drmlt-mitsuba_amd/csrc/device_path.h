@@ -1213,7 +1213,8 @@ DEV void path_begin(const DParams &P, PathState &ps, float v0, float v1) {
 //   the shadow ray of the SAME vertex concurrently; `shadow_clear` is the partner's result for the
 //   ray handed over in the previous step (`sr`), so a bounce costs one step instead of two. The
 //   order of the radiance additions is the same in both modes (NEE of vertex i, then MIS of i+1).
-// FEAT: scene features compiled in (bit 0 rough conductor, bit 1 dielectric, bit 2 spheres, bit 3 BVH); kernels for
+// FEAT: scene features compiled in (bit 0 rough conductor, bit 1 dielectric, bit 2 what is not a polygon: spheres and point
+// lights, bit 3 BVH); kernels for
 // plain diffuse polygon scenes (the Cornell configs) carry none of the other code or its registers.
 // HAS_BEGIN = false: the caller starts every path with path_begin itself (k_mutate_v4: in its bookkeeping branch), the
 // step never sees PH_BEGIN and carries none of its code.
@@ -1349,6 +1350,8 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
             f3 lp;
             if ((L.bsdf >> 24) == PRIM_RECTANGLE) { // rectangle.cpp:210-216
                 lp = fma3(ld3(L.eu), sx, fma3(ld3(L.ev), sy, ld3(L.origin))); // origin = corner (-1,-1), eu/ev = full edges
+            } else if ((FEAT & 4) && (L.bsdf >> 24) == PRIM_POINT) { // point light: the sample is drawn, not read (point.cpp:131-151)
+                lp = ld3(L.origin);
             } else { // single triangle: squareToUniformTriangle
                 float a = sqrtf(fmaxf(0.f, 1.f - sx));
                 lp = fma3(ld3(L.eu), 1.f - a, fma3(ld3(L.ev), a * sy, ld3(L.origin)));
@@ -1361,6 +1364,10 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
             float pdf = dln != 0.f ? L.inv_area * dist2 / fabsf(dln) : 0.f; // Shape::sampleDirect
             if ((FEAT & 4) && (L.bsdf >> 24) == PRIM_SPHERE) // sphere light: cone sampling, sphere.cpp:286-355
                 sphere_sample_direct(ld3(L.origin), L.eu[0], L.inv_area, p, sx, sy, dd, dist, ln, pdf), dln = dot3(dd, ln);
+            // point light: pdf 1 (discrete), value I / dist^2, no facing test (n = 0); with the pick, value = I / (dist^2 emPdf) and
+            // the MIS weight is 1 (path.cpp:190-218: bsdfPdf = 0 for an emitter that is not on a surface)
+            const bool point = (FEAT & 4) && (L.bsdf >> 24) == PRIM_POINT;
+            if (point) pdf = dist2, dln = -1.f;
             float dr = ps.refn_zero ? 0.f : dot3(dd, n);
             if (dr >= 0.f && dln < 0.f && pdf != 0.f) { // AreaLight::sampleDirect
                 f3 wo = mk3(dot3(dd, s), dot3(dd, t), dot3(dd, n));
@@ -1379,7 +1386,7 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
                     float lpdf = pdf * emPdf;
                     float a = lpdf * lpdf, b = bsdfPdf * bsdfPdf;
                     f3 value = ld3(E.radiance) * (1.f / lpdf);
-                    f3 c = ps.thr * value * bsdfVal * (a / (a + b));
+                    f3 c = ps.thr * value * bsdfVal * (point ? 1.f : a / (a + b));
                     if (!is_zero3(c)) {
                         ps.nee = c;
                         ps.nrays++;

@@ -16,7 +16,9 @@
 
 // PRIM_QUAD2: two triangles (a,b,c), (a,c,d) that form a parallelogram, intersected once; the hit is
 // attributed to the sub-triangle it falls in (two consecutive shading records), so f(u) is unchanged
-enum { PRIM_TRIANGLE = 0, PRIM_RECTANGLE = 1, PRIM_SPHERE = 2, PRIM_QUAD2 = 3 };
+// PRIM_POINT: kind tag of a point light's shading record only (position in `origin`), appended after the primitives' records and
+// reached through DEmitter::prim; no intersection record carries it
+enum { PRIM_TRIANGLE = 0, PRIM_RECTANGLE = 1, PRIM_SPHERE = 2, PRIM_QUAD2 = 3, PRIM_POINT = 4 };
 
 // World -> primitive space affine map (rows), so that one transform serves all three
 // primitive kinds: triangle -> barycentric (u,v,w); rectangle -> Mitsuba object space
@@ -50,7 +52,7 @@ struct DPrimBox {
 };
 
 struct DShade {
-    float origin[3]; // tri: p0; rect: centre; sphere: centre
+    float origin[3]; // tri: p0; rect: centre; sphere: centre; point light: position
     float eu[3];     // tri: p1-p0; rect: objectToWorld column 0; sphere: eu[0] = radius
     float ev[3];     // tri: p2-p0; rect: objectToWorld column 1
     float n[3];      // unit geometric (= shading) normal of flat primitives
@@ -122,7 +124,7 @@ struct DParams {
     int32_t *error_flag;
     int32_t debug;          // DRMLT_DEBUG bit mask (diagnostics only)
     int32_t kernel_variant; // 1: k_mutate (nested loops), 2: k_mutate_v2 (lane state machines), 3: k_mutate_v3 (2 lanes per chain), 4: k_mutate_v4 (free-running, flattened bookkeeping; default)
-    int32_t features;       // bit 0 rough conductor, bit 1 dielectric, bit 2 spheres, bit 3 BVH traversal needed
+    int32_t features;       // bit 0 rough conductor, bit 1 dielectric, bit 2 what is not a polygon (spheres, point lights), bit 3 BVH traversal needed
     int32_t mh_batch;       // k_mutate_v2: parked lanes needed before the bookkeeping branch is taken
     // technique=mmlt (device_bidir.h)
     int32_t technique;        // DRMLT_TECH_*

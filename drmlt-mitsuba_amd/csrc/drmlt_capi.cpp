@@ -222,12 +222,16 @@ std::string build_scene(drmlt_ctx *ctx, const drmlt_scene &s, std::vector<DBsdf>
         bounds.swap(mb);
         geo.swap(mg);
     }
-    // emitters + DiscreteDistribution over sampling weights (scene.cpp m_emitterPDF, pmf.h:109-121)
+    // emitters + DiscreteDistribution over sampling weights (scene.cpp m_emitterPDF, pmf.h:109-121), in the caller's order
+    // (point lights: validate_emitters has checked them)
     double total = 0;
     for (int i = 0; i < s.n_emitters; ++i) {
         const drmlt_emitter &e = s.emitters[i];
-        if (e.type != DRMLT_EMITTER_AREA) return "unsupported emitter type";
-        if (e.shape < 0 || e.shape >= s.n_shapes || s.shapes[e.shape].emitter != i) return "emitter/shape link mismatch";
+        if (e.type == DRMLT_EMITTER_AREA) {
+            if (e.shape < 0 || e.shape >= s.n_shapes || s.shapes[e.shape].emitter != i) return "emitter/shape link mismatch";
+        } else if (e.type != DRMLT_EMITTER_POINT) {
+            return "unsupported emitter type";
+        }
         if (!(e.sampling_weight >= 0)) return "negative emitter sampling weight";
         total += e.sampling_weight;
     }
@@ -241,8 +245,44 @@ std::string build_scene(drmlt_ctx *ctx, const drmlt_scene &s, std::vector<DBsdf>
         DEmitter e{};
         for (int k = 0; k < 3; ++k) e.radiance[k] = s.emitters[i].radiance[k];
         e.prim = s.emitters[i].shape;
+        if (s.emitters[i].type == DRMLT_EMITTER_POINT) { // a shading record of its own behind the primitives' (device_path.h: path_step)
+            DShade sh{};
+            for (int k = 0; k < 3; ++k) sh.origin[k] = s.points[3 * s.emitters[i].shape + k];
+            sh.bsdf = PRIM_POINT << 24;
+            sh.emitter = i;
+            e.prim = (int32_t) ctx->shade.size();
+            ctx->shade.push_back(sh);
+        }
         e.cdf_lo = raw[i]; e.cdf_hi = raw[i + 1];
         emitters.push_back(e);
+    }
+    return "";
+}
+
+// Emitter types and point lights (PointEmitter, point.cpp): what drmlt_create refuses before it looks for a device. Returns ""
+// or an error.
+std::string validate_emitters(const drmlt_scene &s, int technique) {
+    if (s.n_points < 0 || (s.n_points > 0 && !s.points)) return "point lights: n_points must be >= 0 and points non-null";
+    if (s.n_emitters <= 0 || !s.emitters) return "";
+    for (int i = 0; i < s.n_shapes && s.shapes; ++i) {
+        const int ei = s.shapes[i].emitter;
+        if (ei >= 0 && ei < s.n_emitters && s.emitters[ei].type == DRMLT_EMITTER_POINT)
+            return "emitter/shape link mismatch: shape " + std::to_string(i) + " carries point light " + std::to_string(ei);
+    }
+    std::vector<int> owner((size_t) s.n_points, -1);
+    for (int i = 0; i < s.n_emitters; ++i) {
+        const drmlt_emitter &e = s.emitters[i];
+        if (e.type != DRMLT_EMITTER_AREA && e.type != DRMLT_EMITTER_POINT) return "unsupported emitter type " + std::to_string(e.type) + " (supported: area, point)";
+        if (e.type != DRMLT_EMITTER_POINT) continue;
+        const std::string which = "point light " + std::to_string(i) + ": ";
+        if (technique != DRMLT_TECH_PATH) return which + "point lights are supported for technique=path only";
+        if (e.shape < 0 || e.shape >= s.n_points) return which + "position index " + std::to_string(e.shape) + " out of range (n_points = " + std::to_string(s.n_points) + ")";
+        if (owner[(size_t) e.shape] >= 0) return which + "shares position entry " + std::to_string(e.shape) + " with emitter " + std::to_string(owner[(size_t) e.shape]);
+        owner[(size_t) e.shape] = i;
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(s.points[3 * e.shape + k])) return which + "position is not finite";
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(e.radiance[k]) || e.radiance[k] < 0.f) return which + "intensity must be finite and non-negative";
     }
     return "";
 }
@@ -318,8 +358,13 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
         return nullptr;
     };
     if (!cfg || !scene) return bail(nullptr, "null config or scene");
-    if (cfg->struct_size != sizeof(drmlt_config) || scene->struct_size != sizeof(drmlt_scene))
+    if (cfg->struct_size != sizeof(drmlt_config) || (scene->struct_size != sizeof(drmlt_scene) && scene->struct_size != DRMLT_SCENE_SIZE_NO_POINTS))
         return bail(nullptr, "struct_size mismatch (ABI version skew)");
+    // a scene that ends at `camera` has no point lights: nothing behind `camera` is read (its tail padding is where n_points lies)
+    drmlt_scene scene_in;
+    memset(&scene_in, 0, sizeof scene_in);
+    memcpy(&scene_in, scene, scene->struct_size == sizeof(drmlt_scene) ? sizeof(drmlt_scene) : offsetof(drmlt_scene, camera) + sizeof(drmlt_camera));
+    scene = &scene_in;
     // ---- parameter checks of the DRMLT ctor / PathSampler ctor (drmlt.cpp:193-349, pathsampler.cpp:57-71)
     if (cfg->algo != DRMLT_ALGO_DRMLT && cfg->algo != DRMLT_ALGO_PSSMLT) return bail(nullptr, "Unknown algorithm");
     if (cfg->algo == DRMLT_ALGO_PSSMLT && cfg->technique != DRMLT_TECH_PATH)
@@ -346,6 +391,8 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     if (mmlt && cfg->timid_after_large) return bail(nullptr, "timidAfterLarge is not defined for technique=mmlt");
     if (cfg->sample_count <= 0) return bail(nullptr, "sample_count must be positive");
     if (!(cfg->p_large >= 0.f && cfg->p_large <= 1.f)) return bail(nullptr, "pLarge must be in [0,1]");
+    const std::string point_err = validate_emitters(*scene, cfg->technique);
+    if (!point_err.empty()) return bail(nullptr, point_err);
     const drmlt_camera &cam = scene->camera;
     if (cam.width <= 0 || cam.height <= 0) return bail(nullptr, "film size must be positive");
     if (cam.filter != DRMLT_FILTER_BOX && cam.filter != DRMLT_FILTER_GAUSSIAN) return bail(nullptr, "unsupported reconstruction filter");
@@ -605,6 +652,7 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     P.features = 0;
     for (const DBsdf &b : bsdfs) P.features |= b.type == DRMLT_BSDF_ROUGHCONDUCTOR ? 1 : (b.type == DRMLT_BSDF_DIELECTRIC ? 2 : 0);
     for (const DPrim &g : ctx->prims) if (g.type == PRIM_SPHERE) P.features |= 4;
+    for (int i = 0; i < scene->n_emitters; ++i) if (scene->emitters[i].type == DRMLT_EMITTER_POINT) P.features |= 4; // what is not a polygon
     if (P.use_bvh) P.features |= 8;
     if (getenv("DRMLT_FEAT_ALL")) P.features = 15;
     // the ray-pool kernel keeps ONE proposal row group in LDS: Green's reverse move and Mira's ratio, which need x, y and z together,

@@ -52,11 +52,14 @@ private:
     std::map<std::string, std::string> m_;
 };
 
-// Flat scene as written by SceneData.save() (drmlt-mitsuba_amd/scenes.py): the arrays of drmlt_scene
+// Flat scene as written by SceneData.save() (drmlt-mitsuba_amd/scenes.py): the arrays of drmlt_scene. The point lights'
+// positions, if the scene has any, follow the camera as a trailing block: "PNTS", a count, xyz floats per light.
 struct SceneFile {
+    static constexpr uint32_t POINTS_TAG = 0x53544E50u; /* "PNTS" */
     std::vector<drmlt_shape> shapes;
     std::vector<drmlt_bsdf> bsdfs;
     std::vector<drmlt_emitter> emitters;
+    std::vector<float> points;
     drmlt_camera camera{};
     drmlt_scene view() const {
         drmlt_scene s;
@@ -66,6 +69,7 @@ struct SceneFile {
         s.n_bsdfs = (int32_t) bsdfs.size(); s.bsdfs = bsdfs.data();
         s.n_emitters = (int32_t) emitters.size(); s.emitters = emitters.data();
         s.camera = camera;
+        s.n_points = (int32_t) (points.size() / 3); s.points = points.empty() ? nullptr : points.data();
         return s;
     }
     static SceneFile load(const std::string &path) {
@@ -81,6 +85,14 @@ struct SceneFile {
                  fread(sf.bsdfs.data(), sizeof(drmlt_bsdf), hdr[3], f) == hdr[3] &&
                  fread(sf.emitters.data(), sizeof(drmlt_emitter), hdr[4], f) == hdr[4] &&
                  fread(&sf.camera, sizeof sf.camera, 1, f) == 1;
+        }
+        uint32_t blk[2];
+        if (ok && fread(blk, sizeof blk, 1, f) == 1) { // optional point-light block; a file without it ends at the camera
+            ok = blk[0] == POINTS_TAG && blk[1] <= (1u << 24);
+            if (ok) {
+                sf.points.resize((size_t) blk[1] * 3);
+                ok = fread(sf.points.data(), sizeof(float), sf.points.size(), f) == sf.points.size();
+            }
         }
         fclose(f);
         if (!ok) throw std::runtime_error("malformed scene file " + path);

@@ -53,10 +53,14 @@ def lookat(origin, target, up):
     return m
 
 
+POINTS_TAG = 0x53544E50  # "PNTS": the point-light block of a scene file (SceneData.save)
+
+
 class SceneData:
     def __init__(self, name):
         self.name = name
         self.shapes, self.bsdfs, self.emitters = [], [], []
+        self.points = []   # positions of the point lights (drmlt_scene.points)
         self.camera = abi.Camera()
         self._keep = None
 
@@ -127,6 +131,18 @@ class SceneData:
         self.shapes.append(s)
         return len(self.shapes) - 1
 
+    def point_light(self, position, intensity=1.0, sampling_weight=1.0):
+        """Mitsuba `point` emitter (src/emitters/point.cpp): intensity in W/sr, default (1, 1, 1) (Spectrum::getD65() in RGB
+        builds). Takes the next emitter index, so the sampling order is the order of the calls. technique=path only."""
+        e = abi.Emitter()
+        e.type = abi.EMITTER_POINT
+        e.shape = len(self.points)
+        e.radiance[:] = intensity if hasattr(intensity, "__len__") else (intensity,) * 3
+        e.sampling_weight = sampling_weight
+        self.points.append(tuple(float(v) for v in position))
+        self.emitters.append(e)
+        return len(self.emitters) - 1
+
     def box(self, to_world, bsdf):
         """Mitsuba `cube`: [-1,1]^3 under to_world, 12 outward-facing triangles."""
         m = np.asarray(to_world, dtype=np.float64)
@@ -145,7 +161,9 @@ class SceneData:
         c.width, c.height, c.filter, c.filter_param = width, height, filt, filter_param
 
     def save(self, path):
-        """Flat binary scene file read by the C++ host (host/drmlt_integrator.hpp: SceneFile::load)."""
+        """Flat binary scene file read by the C++ host (host/drmlt_integrator.hpp: SceneFile::load). Point lights follow the
+        camera as a trailing block ("PNTS", count, xyz float32 each), written only when there are any: a scene without them
+        gives the same bytes as before the block existed."""
         import struct as _st
         with open(path, "wb") as f:
             f.write(_st.pack("<8I", 0x4C4D5244, abi.ABI_VERSION, len(self.shapes), len(self.bsdfs), len(self.emitters),
@@ -154,6 +172,9 @@ class SceneData:
                 for item in group:
                     f.write(bytes(item))
             f.write(bytes(self.camera))
+            if self.points:
+                f.write(_st.pack("<2I", POINTS_TAG, len(self.points)))
+                f.write(np.asarray(self.points, dtype="<f4").tobytes())
 
     def struct(self):
         sh = (abi.Shape * len(self.shapes))(*self.shapes)
@@ -166,7 +187,10 @@ class SceneData:
         s.bsdfs = C.cast(bs, C.POINTER(abi.Bsdf))
         s.emitters = C.cast(em, C.POINTER(abi.Emitter))
         s.camera = self.camera
-        self._keep = (sh, bs, em)
+        pts = (C.c_float * max(3, 3 * len(self.points)))(*[v for p in self.points for v in p])
+        s.n_points = len(self.points)
+        s.points = C.cast(pts, C.POINTER(C.c_float))
+        self._keep = (sh, bs, em, pts)
         return s
 
 
@@ -284,5 +308,24 @@ def caustic_c5(res=128):
     return sd
 
 
+def cornell_point(res=512, filt=abi.FILTER_BOX, quad_light=False, point_weight=1.0):
+    """C2's box lit by a point light under the ceiling (BASELINE config 5 names a point light; technique=path).
+    quad_light: keep C2's ceiling quad light as well, emitter 0 -- the point light (sampling weight `point_weight`) is
+    emitter 1."""
+    sd = SceneData("cornell_point")
+    white = sd.diffuse(0.725, 0.71, 0.68)
+    red = sd.diffuse(0.63, 0.065, 0.05)
+    green = sd.diffuse(0.14, 0.45, 0.091)
+    black = sd.diffuse(0.0)
+    _room(sd, white, red, green)
+    sd.box(translate(-0.33, -0.4, -0.3) @ rotate("y", 17) @ scale(0.3, 0.6, 0.3), white)
+    sd.box(translate(0.33, -0.7, 0.3) @ rotate("y", -17) @ scale(0.3, 0.3, 0.3), white)
+    if quad_light:
+        sd.rectangle(translate(0, 0.995, 0) @ rotate("x", 90) @ scale(0.25), black, radiance=(17.0, 12.0, 4.0))
+    sd.point_light((0.0, 0.8, 0.0), intensity=(4.0, 3.2, 2.0), sampling_weight=point_weight)
+    sd.set_camera(lookat((0, 0, 3.9), (0, 0, 0), (0, 1, 0)), 39.3077, res, res, filt, 0.5)
+    return sd
+
+
 SCENES = {"cornell_c1": cornell_c1, "cornell_c2": cornell_c2, "glass_sphere": glass_sphere, "door_c3": door_c3,
-          "triangle_soup": triangle_soup, "caustic_c5": caustic_c5}
+          "triangle_soup": triangle_soup, "caustic_c5": caustic_c5, "cornell_point": cornell_point}

@@ -65,7 +65,10 @@ enum {
     DRMLT_BSDF_ROUGHCONDUCTOR = 2  /* src/bsdfs/roughconductor.cpp */
 };
 
-enum { DRMLT_EMITTER_AREA = 0 };   /* src/emitters/area.cpp */
+enum {
+    DRMLT_EMITTER_AREA = 0,   /* src/emitters/area.cpp  */
+    DRMLT_EMITTER_POINT = 1   /* src/emitters/point.cpp (technique=path only) */
+};
 
 enum { DRMLT_FILTER_BOX = 0, DRMLT_FILTER_GAUSSIAN = 1 };
 
@@ -157,10 +160,15 @@ typedef struct drmlt_bsdf {
     float   p[8];
 } drmlt_bsdf;
 
+/* AREA:  `shape` is the index of the shape carrying the emitter, `radiance` its radiance.
+ * POINT: `shape` is the index of the light's position in drmlt_scene.points (one emitter per entry), `radiance` its
+ *        intensity in W/sr ("intensity", default Spectrum::getD65() = (1, 1, 1) in RGB builds). Sampled as
+ *        PointEmitter::sampleDirect (point.cpp:131-151): a delta position, MIS weight 1, never hit by a ray.
+ * The emitters' order is the order of the sampling distribution (Scene::m_emitterPDF over the sampling weights). */
 typedef struct drmlt_emitter {
-    int32_t type;        /* DRMLT_EMITTER_AREA                        */
-    int32_t shape;       /* index of the shape carrying this emitter */
-    float   radiance[3];
+    int32_t type;        /* DRMLT_EMITTER_*                           */
+    int32_t shape;       /* AREA: shape index; POINT: position index  */
+    float   radiance[3]; /* AREA: radiance; POINT: intensity          */
     float   sampling_weight; /* Emitter::getSamplingWeight, default 1 */
 } drmlt_emitter;
 
@@ -175,6 +183,8 @@ typedef struct drmlt_camera {
     float   filter_param;   /* box: radius (0.5); gaussian: stddev (0.5)      */
 } drmlt_camera;
 
+/* struct_size: sizeof(drmlt_scene), or DRMLT_SCENE_SIZE_NO_POINTS -- the layout that ends at `camera` (callers
+ * built before the point-light fields), which means "no point lights": the trailing fields are then not read. */
 typedef struct drmlt_scene {
     uint32_t struct_size;       /* = sizeof(drmlt_scene) */
     int32_t  n_shapes;
@@ -184,7 +194,13 @@ typedef struct drmlt_scene {
     const drmlt_bsdf    *bsdfs;
     const drmlt_emitter *emitters;
     drmlt_camera camera;
+    int32_t  n_points;          /* positions of the POINT emitters           */
+    const float *points;        /* xyz per point light (3 * n_points floats) */
 } drmlt_scene;
+
+/* sizeof(drmlt_scene) up to and including `camera`, padded to the struct's alignment */
+#define DRMLT_SCENE_SIZE_NO_POINTS \
+    ((offsetof(drmlt_scene, camera) + sizeof(drmlt_camera) + sizeof(void *) - 1) / sizeof(void *) * sizeof(void *))
 
 /* ---- statistics: numerators / denominators of drmlt_proc.cpp:34-49 ----- */
 

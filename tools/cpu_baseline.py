@@ -94,9 +94,21 @@ def scene_to_xml(pkg, sd, conf, out_dir, name):
             x.append('  <bsdf type="roughconductor" id="b%d"><string name="distribution" value="%s"/><float name="alpha" value="%.7g"/>'
                      '<float name="extEta" value="1"/><spectrum name="eta" value="%.7g, %.7g, %.7g"/><spectrum name="k" value="%.7g, %.7g, %.7g"/>'
                      '<spectrum name="specularReflectance" value="%.7g, %.7g, %.7g"/></bsdf>' % (i, "ggx" if b.p[7] else "beckmann", b.p[0], *list(b.p)[1:7], *b.rgb))
+    # emitters enter Mitsuba's m_emitters (the order of the sampling PMF) in document order: a point light goes out before the
+    # first shape that carries an emitter of a higher index
+    points = [i for i, e in enumerate(sd.emitters) if e.type == abi.EMITTER_POINT]
+
+    def point_lights_before(k):
+        while points and points[0] < k:
+            e = sd.emitters[points.pop(0)]
+            x.append('  <emitter type="point"><point name="position" x="%.9g" y="%.9g" z="%.9g"/><spectrum name="intensity" value="%.7g, %.7g, %.7g"/>'
+                     '<float name="samplingWeight" value="%.7g"/></emitter>' % (*sd.points[e.shape], *e.radiance, e.sampling_weight))
+
     n_obj = 0
     for s in sd.shapes:
         em = ""
+        if s.emitter >= 0:
+            point_lights_before(s.emitter)
         if s.emitter >= 0:
             e = sd.emitters[s.emitter]
             em = '<emitter type="area"><spectrum name="radiance" value="%.7g, %.7g, %.7g"/><float name="samplingWeight" value="%.7g"/></emitter>' % (*e.radiance, e.sampling_weight)
@@ -112,6 +124,7 @@ def scene_to_xml(pkg, sd, conf, out_dir, name):
                     f.write("v %.9g %.9g %.9g\n" % tuple(list(s.data)[3 * v:3 * v + 3]))
                 f.write("f 1 2 3\n")
             x.append('  <shape type="obj"><string name="filename" value="%s"/><boolean name="faceNormals" value="true"/><ref id="b%d"/>%s</shape>' % (fn, s.bsdf, em))
+    point_lights_before(len(sd.emitters))
     c = sd.camera
     filt = ('<rfilter type="box"><float name="radius" value="%.7g"/></rfilter>' % c.filter_param) if c.filter == abi.FILTER_BOX else \
            ('<rfilter type="gaussian"><float name="stddev" value="%.7g"/></rfilter>' % c.filter_param)
