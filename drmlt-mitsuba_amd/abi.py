@@ -7,6 +7,7 @@ ALGO_DRMLT, ALGO_PSSMLT = 0, 1
 SHAPE_TRIANGLE, SHAPE_RECTANGLE, SHAPE_SPHERE = 0, 1, 2
 BSDF_DIFFUSE, BSDF_DIELECTRIC, BSDF_ROUGHCONDUCTOR, BSDF_CONDUCTOR = 0, 1, 2, 3
 EMITTER_AREA, EMITTER_POINT = 0, 1   # src/emitters/area.cpp, src/emitters/point.cpp (technique=path only)
+EMITTER_CONSTANT = 2                 # src/emitters/constant.cpp: environment of constant radiance (technique=path only, one per scene)
 FILTER_BOX, FILTER_GAUSSIAN = 0, 1
 SEED_TARGET, SEED_REFERENCE = 0, 1            # drmlt_config.seed_rule (two-stage MLT seeding)
 WORK_UNITS_DEVICE, WORK_UNITS_REFERENCE = 0, 1  # drmlt_config.work_units_rule (what workUnits = -1 derives)

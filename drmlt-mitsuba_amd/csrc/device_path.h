@@ -1158,6 +1158,30 @@ DEV f3 square_to_cosine_hemisphere(float sx, float sy) {
     return mk3(px, py, z);
 }
 
+// Constant environment seen from `ref` (ConstantBackgroundEmitter::sampleDirect, constant.cpp:173-214; refN = the shading normal
+// `n`): a cosine-weighted direction in Frame(n) (coordinateSystem, util.cpp:606-616), its solid-angle pdf cos / pi, and the
+// distance to the far side of the scene's bounding sphere (BSphere::rayIntersect + solveQuadratic, util.cpp:447-485). pdf = 0
+// (the sample is dropped) unless `ref` lies inside the sphere. The refN = 0 case (uniform sphere) has no caller: only the
+// dielectric zeroes refN, and it draws no light sample.
+DEV void env_sample_direct(f3 c, float radius, f3 ref, f3 n, float sx, float sy, f3 &d, float &dist, float &pdf) {
+    const f3 w = square_to_cosine_hemisphere(sx, sy);
+    f3 fs, ft;
+    if (fabsf(n.x) > fabsf(n.y)) { float inv = rsqrtf(n.x * n.x + n.z * n.z); ft = mk3(n.z * inv, 0.f, -n.x * inv); }
+    else { float inv = rsqrtf(n.y * n.y + n.z * n.z); ft = mk3(0.f, n.z * inv, -n.y * inv); }
+    fs = cross3(ft, n);
+    d = fma3(fs, w.x, fma3(ft, w.y, n * w.z));
+    pdf = INV_PI_F * w.z;
+    const f3 o = ref - c;
+    const float A = dot3(d, d), B = 2.f * dot3(o, d), C = dot3(o, o) - radius * radius;
+    const float discrim = B * B - 4.f * A * C;
+    const float sq = sqrtf(fmaxf(discrim, 0.f));
+    const float temp = B < 0.f ? -0.5f * (B - sq) : -0.5f * (B + sq);
+    const float x0 = temp / A, x1 = C / temp;
+    const float nearT = fminf(x0, x1), farT = fmaxf(x0, x1);
+    dist = farT;
+    if (!(discrim >= 0.f && nearT < 0.f && farT > 0.f)) pdf = 0.f;
+}
+
 // util.cpp:659-689
 DEV float fresnel_dielectric_ext(float cosThetaI_, float &cosThetaT_, float eta) {
     if (eta == 1.f) { cosThetaT_ = -cosThetaI_; return 0.f; }
@@ -1213,8 +1237,8 @@ DEV void path_begin(const DParams &P, PathState &ps, float v0, float v1) {
 //   the shadow ray of the SAME vertex concurrently; `shadow_clear` is the partner's result for the
 //   ray handed over in the previous step (`sr`), so a bounce costs one step instead of two. The
 //   order of the radiance additions is the same in both modes (NEE of vertex i, then MIS of i+1).
-// FEAT: scene features compiled in (bit 0 rough conductor, bit 1 dielectric, bit 2 what is not a polygon: spheres and point
-// lights, bit 3 BVH); kernels for
+// FEAT: scene features compiled in (bit 0 rough conductor, bit 1 dielectric, bit 2 what is not a polygon: spheres, point
+// lights and the environment, bit 3 BVH); kernels for
 // plain diffuse polygon scenes (the Cornell configs) carry none of the other code or its registers.
 // HAS_BEGIN = false: the caller starts every path with path_begin itself (k_mutate_v4: in its bookkeeping branch), the
 // step never sees PH_BEGIN and carries none of its code.
@@ -1249,7 +1273,22 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
         if (hit.prim < 0) ps.Li = ps.Li + ps.nee; // unoccluded
         B = T.bsdf(ps.bsdf);
     } else {
-        if (hit.prim < 0) { ps.phase = PH_DONE; return; } // no environment emitter
+        if (hit.prim < 0) { // the ray left the scene
+            if ((FEAT & 4) && P.env_emitter >= 0 && ps.has_bounce) { // environment seen by a BSDF-sampled ray (path.cpp:253-262, 275-285)
+                ps.thr = ps.thr * ps.bweight;
+                // the emitter-hit branch's gates: directTracing = false, so a camera ray that misses (has_bounce) or an escape after
+                // delta vertices only (non_specular) adds nothing
+                if (ps.direct_on && ps.non_specular) {
+                    const DEmitter E = T.emitter(P.env_emitter);
+                    // pdfEmitterDirect with the previous vertex's refN (ps.n; only the dielectric zeroes it, and it is delta: lumPdf = 0)
+                    const float lumPdf = ps.bdelta ? 0.f : INV_PI_F * fmaxf(0.f, dot3(ps.d, ps.n)) * (E.cdf_hi - E.cdf_lo);
+                    float a = ps.bpdf * ps.bpdf, b = lumPdf * lumPdf;
+                    ps.Li = fma3(ps.thr * ld3(E.radiance), a / (a + b), ps.Li);
+                }
+            }
+            ps.phase = PH_DONE;
+            return;
+        }
         const DShade S = T.shade(hit.prim);
         const int ptype = S.bsdf >> 24; // primitive kind rides in the top byte
         // surface point + shading frame (skdtree.h:340-429, rectangle.cpp:155-168, sphere.cpp:207-255)
@@ -1364,6 +1403,10 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
             float pdf = dln != 0.f ? L.inv_area * dist2 / fabsf(dln) : 0.f; // Shape::sampleDirect
             if ((FEAT & 4) && (L.bsdf >> 24) == PRIM_SPHERE) // sphere light: cone sampling, sphere.cpp:286-355
                 sphere_sample_direct(ld3(L.origin), L.eu[0], L.inv_area, p, sx, sy, dd, dist, ln, pdf), dln = dot3(dd, ln);
+            // environment: cosine-weighted about n, pdf cos / pi in solid angle, no facing test; MIS (power heuristic) against the BSDF
+            // as for area lights (path.cpp:203-211: the emitter is on a surface, the measure is solid angle)
+            if ((FEAT & 4) && (L.bsdf >> 24) == PRIM_ENV)
+                env_sample_direct(ld3(L.origin), L.eu[0], p, n, sx, sy, dd, dist, pdf), dln = -1.f;
             // point light: pdf 1 (discrete), value I / dist^2, no facing test (n = 0); with the pick, value = I / (dist^2 emPdf) and
             // the MIS weight is 1 (path.cpp:190-218: bsdfPdf = 0 for an emitter that is not on a surface)
             const bool point = (FEAT & 4) && (L.bsdf >> 24) == PRIM_POINT;

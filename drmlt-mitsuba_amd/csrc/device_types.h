@@ -18,7 +18,8 @@
 // attributed to the sub-triangle it falls in (two consecutive shading records), so f(u) is unchanged
 // PRIM_POINT: kind tag of a point light's shading record only (position in `origin`), appended after the primitives' records and
 // reached through DEmitter::prim; no intersection record carries it
-enum { PRIM_TRIANGLE = 0, PRIM_RECTANGLE = 1, PRIM_SPHERE = 2, PRIM_QUAD2 = 3, PRIM_POINT = 4 };
+// PRIM_ENV: the same for the constant environment emitter (the scene's bounding sphere: centre in `origin`, radius in eu[0])
+enum { PRIM_TRIANGLE = 0, PRIM_RECTANGLE = 1, PRIM_SPHERE = 2, PRIM_QUAD2 = 3, PRIM_POINT = 4, PRIM_ENV = 5 };
 
 // World -> primitive space affine map (rows), so that one transform serves all three
 // primitive kinds: triangle -> barycentric (u,v,w); rectangle -> Mitsuba object space
@@ -52,8 +53,8 @@ struct DPrimBox {
 };
 
 struct DShade {
-    float origin[3]; // tri: p0; rect: centre; sphere: centre; point light: position
-    float eu[3];     // tri: p1-p0; rect: objectToWorld column 0; sphere: eu[0] = radius
+    float origin[3]; // tri: p0; rect: centre; sphere: centre; point light: position; environment: bounding sphere's centre
+    float eu[3];     // tri: p1-p0; rect: objectToWorld column 0; sphere, environment: eu[0] = radius
     float ev[3];     // tri: p2-p0; rect: objectToWorld column 1
     float n[3];      // unit geometric (= shading) normal of flat primitives
     float inv_len_eu;
@@ -124,7 +125,7 @@ struct DParams {
     int32_t *error_flag;
     int32_t debug;          // DRMLT_DEBUG bit mask (diagnostics only)
     int32_t kernel_variant; // 1: k_mutate (nested loops), 2: k_mutate_v2 (lane state machines), 3: k_mutate_v3 (2 lanes per chain), 4: k_mutate_v4 (free-running, flattened bookkeeping; default)
-    int32_t features;       // bit 0 rough conductor, bit 1 dielectric, bit 2 what is not a polygon (spheres, point lights), bit 3 BVH traversal needed
+    int32_t features;       // bit 0 rough conductor, bit 1 dielectric, bit 2 what is not a polygon (spheres, point lights, environment), bit 3 BVH traversal needed
     int32_t mh_batch;       // k_mutate_v2: parked lanes needed before the bookkeeping branch is taken
     // technique=mmlt (device_bidir.h)
     int32_t technique;        // DRMLT_TECH_*
@@ -164,7 +165,7 @@ struct DParams {
     int32_t n_box;
     int32_t n_flat_rec;          // records in prims_flat (flat records that are no cuboid's face) -- n_flat counts the flat records of `prims`
     int32_t small_tables_lds;    // k_mutate_v5 on traversed scenes: BSDF / emitter records and the emitters' shape records are staged in LDS (they fit beside the pool)
-    int32_t pad_tables;
+    int32_t env_emitter;         // index of the constant environment emitter (read under feature bit 4 only), or -1: a ray that leaves the scene ends the path
     float *rows;                 // k_mutate_v5 with its proposal rows in device memory ([dim][chain], as x), or NULL: rows in LDS
     int32_t boot_weighted;       // bootstrap kernels: also write each sample's luminance under the importance map, to lum_out[n + i] (two-stage MLT: seeds drawn from the chains' own target, drmlt_capi.cpp)
 };

@@ -75,6 +75,23 @@ bool invert3x4(const double *m, double *o) {
     return true;
 }
 
+// ConstantBackgroundEmitter::createShape (constant.cpp:67-92): the bounding sphere of the scene's box, its radius times 1.5 (at least
+// Epsilon). The box is the geometry's (the kd-tree's) expanded by the sensor's position: DRMLT calls Scene::initializeBidirectional
+// (scene.cpp:396-423), which builds it before any emitter's shape. AABB::getBSphere: the box's centre, the distance to its max
+// corner. Only the length of the light sample's shadow ray depends on it.
+void scene_bsphere(const drmlt_scene &s, const std::vector<PrimBounds> &bounds, float centre[3], float &radius) {
+    const double cam[3] = {s.camera.to_world[3], s.camera.to_world[7], s.camera.to_world[11]};
+    double lo[3], hi[3], r2 = 0;
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = hi[k] = cam[k];
+        for (const PrimBounds &b : bounds) { lo[k] = std::min(lo[k], (double) b.lo[k]); hi[k] = std::max(hi[k], (double) b.hi[k]); }
+        const double c = 0.5 * (lo[k] + hi[k]);
+        centre[k] = (float) c;
+        r2 += (hi[k] - c) * (hi[k] - c);
+    }
+    radius = (float) std::max(1e-4, 1.5 * std::sqrt(r2)); // Epsilon (single precision builds)
+}
+
 // Flatten the scene into intersection + shading records. Returns "" or an error.
 std::string build_scene(drmlt_ctx *ctx, const drmlt_scene &s, std::vector<DBsdf> &bsdfs, std::vector<DEmitter> &emitters,
                         std::vector<PrimBounds> &bounds, std::vector<QuadGeo> &geo) {
@@ -229,7 +246,7 @@ std::string build_scene(drmlt_ctx *ctx, const drmlt_scene &s, std::vector<DBsdf>
         const drmlt_emitter &e = s.emitters[i];
         if (e.type == DRMLT_EMITTER_AREA) {
             if (e.shape < 0 || e.shape >= s.n_shapes || s.shapes[e.shape].emitter != i) return "emitter/shape link mismatch";
-        } else if (e.type != DRMLT_EMITTER_POINT) {
+        } else if (e.type != DRMLT_EMITTER_POINT && e.type != DRMLT_EMITTER_CONSTANT) {
             return "unsupported emitter type";
         }
         if (!(e.sampling_weight >= 0)) return "negative emitter sampling weight";
@@ -253,14 +270,22 @@ std::string build_scene(drmlt_ctx *ctx, const drmlt_scene &s, std::vector<DBsdf>
             e.prim = (int32_t) ctx->shade.size();
             ctx->shade.push_back(sh);
         }
+        if (s.emitters[i].type == DRMLT_EMITTER_CONSTANT) { // the same for the environment: the scene's bounding sphere
+            DShade sh{};
+            scene_bsphere(s, bounds, sh.origin, sh.eu[0]);
+            sh.bsdf = PRIM_ENV << 24;
+            sh.emitter = i;
+            e.prim = (int32_t) ctx->shade.size();
+            ctx->shade.push_back(sh);
+        }
         e.cdf_lo = raw[i]; e.cdf_hi = raw[i + 1];
         emitters.push_back(e);
     }
     return "";
 }
 
-// Emitter types and point lights (PointEmitter, point.cpp): what drmlt_create refuses before it looks for a device. Returns ""
-// or an error.
+// Emitter types, point lights (PointEmitter, point.cpp) and the environment (ConstantBackgroundEmitter, constant.cpp): what
+// drmlt_create refuses before it looks for a device. Returns "" or an error.
 std::string validate_emitters(const drmlt_scene &s, int technique) {
     if (s.n_points < 0 || (s.n_points > 0 && !s.points)) return "point lights: n_points must be >= 0 and points non-null";
     if (s.n_emitters <= 0 || !s.emitters) return "";
@@ -268,11 +293,25 @@ std::string validate_emitters(const drmlt_scene &s, int technique) {
         const int ei = s.shapes[i].emitter;
         if (ei >= 0 && ei < s.n_emitters && s.emitters[ei].type == DRMLT_EMITTER_POINT)
             return "emitter/shape link mismatch: shape " + std::to_string(i) + " carries point light " + std::to_string(ei);
+        if (ei >= 0 && ei < s.n_emitters && s.emitters[ei].type == DRMLT_EMITTER_CONSTANT)
+            return "emitter/shape link mismatch: shape " + std::to_string(i) + " carries the environment emitter " + std::to_string(ei);
     }
     std::vector<int> owner((size_t) s.n_points, -1);
+    int env = -1;
     for (int i = 0; i < s.n_emitters; ++i) {
         const drmlt_emitter &e = s.emitters[i];
-        if (e.type != DRMLT_EMITTER_AREA && e.type != DRMLT_EMITTER_POINT) return "unsupported emitter type " + std::to_string(e.type) + " (supported: area, point)";
+        if (e.type != DRMLT_EMITTER_AREA && e.type != DRMLT_EMITTER_POINT && e.type != DRMLT_EMITTER_CONSTANT)
+            return "unsupported emitter type " + std::to_string(e.type) + " (supported: area, point, constant)";
+        if (e.type == DRMLT_EMITTER_CONSTANT) { // ConstantBackgroundEmitter (constant.cpp)
+            const std::string which = "environment emitter " + std::to_string(i) + ": ";
+            if (env >= 0) return which + "the scene may only contain one environment emitter (emitter " + std::to_string(env) + " is one)";
+            env = i;
+            if (technique != DRMLT_TECH_PATH) return which + "environment emitters are supported for technique=path only";
+            if (e.shape != -1) return which + "shape must be -1 (it has no shape), got " + std::to_string(e.shape);
+            for (int k = 0; k < 3; ++k)
+                if (!std::isfinite(e.radiance[k]) || e.radiance[k] < 0.f) return which + "radiance must be finite and non-negative";
+            continue;
+        }
         if (e.type != DRMLT_EMITTER_POINT) continue;
         const std::string which = "point light " + std::to_string(i) + ": ";
         if (technique != DRMLT_TECH_PATH) return which + "point lights are supported for technique=path only";
@@ -652,7 +691,11 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     P.features = 0;
     for (const DBsdf &b : bsdfs) P.features |= b.type == DRMLT_BSDF_ROUGHCONDUCTOR ? 1 : (b.type == DRMLT_BSDF_DIELECTRIC ? 2 : 0);
     for (const DPrim &g : ctx->prims) if (g.type == PRIM_SPHERE) P.features |= 4;
-    for (int i = 0; i < scene->n_emitters; ++i) if (scene->emitters[i].type == DRMLT_EMITTER_POINT) P.features |= 4; // what is not a polygon
+    P.env_emitter = -1;
+    for (int i = 0; i < scene->n_emitters; ++i) {
+        if (scene->emitters[i].type == DRMLT_EMITTER_POINT) P.features |= 4; // what is not a polygon
+        if (scene->emitters[i].type == DRMLT_EMITTER_CONSTANT) P.features |= 4, P.env_emitter = i;
+    }
     if (P.use_bvh) P.features |= 8;
     if (getenv("DRMLT_FEAT_ALL")) P.features = 15;
     // the ray-pool kernel keeps ONE proposal row group in LDS: Green's reverse move and Mira's ratio, which need x, y and z together,
@@ -692,7 +735,6 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
         const size_t small = ((size_t) P.n_bsdfs * 12 + (size_t) P.n_emitters * 24) * sizeof(float);
         const size_t room = P.rows ? (P.bvh_stack16 ? 1536 : 1024) : (P.bvh_stack16 ? 768 : 0);
         P.small_tables_lds = (P.use_bvh && P.kernel_variant == 5 && small <= room && !getenv("DRMLT_NO_SMALL_TABLES")) ? 1 : 0;
-        P.pad_tables = 0;
     }
     P.bvh_overflow = nullptr; P.bvh_ovf_lanes = 0;
     P.exec_order = nullptr;

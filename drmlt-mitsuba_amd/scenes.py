@@ -143,6 +143,18 @@ class SceneData:
         self.emitters.append(e)
         return len(self.emitters) - 1
 
+    def constant_environment(self, radiance=1.0, sampling_weight=1.0):
+        """Mitsuba `constant` emitter (src/emitters/constant.cpp): radiance seen by every ray that leaves the scene, default
+        (1, 1, 1) (Spectrum::getD65() in RGB builds). It has no shape (`shape` = -1) and takes the next emitter index, so its
+        place in the sampling order is the order of the calls. At most one per scene; technique=path only."""
+        e = abi.Emitter()
+        e.type = abi.EMITTER_CONSTANT
+        e.shape = -1
+        e.radiance[:] = radiance if hasattr(radiance, "__len__") else (radiance,) * 3
+        e.sampling_weight = sampling_weight
+        self.emitters.append(e)
+        return len(self.emitters) - 1
+
     def box(self, to_world, bsdf):
         """Mitsuba `cube`: [-1,1]^3 under to_world, 12 outward-facing triangles."""
         m = np.asarray(to_world, dtype=np.float64)
@@ -327,5 +339,24 @@ def cornell_point(res=512, filt=abi.FILTER_BOX, quad_light=False, point_weight=1
     return sd
 
 
+def cornell_sky(res=512, filt=abi.FILTER_BOX, quad_light=False, env_weight=1.0):
+    """C2's room, open at the front, under a constant sky of radiance (0.9, 1.0, 1.2) (technique=path): light reaches the room
+    through the opening. quad_light: keep C2's ceiling quad light as well, emitter 0 -- the sky (sampling weight `env_weight`)
+    is then emitter 1."""
+    sd = SceneData("cornell_sky")
+    white = sd.diffuse(0.725, 0.71, 0.68)
+    red = sd.diffuse(0.63, 0.065, 0.05)
+    green = sd.diffuse(0.14, 0.45, 0.091)
+    black = sd.diffuse(0.0)
+    _room(sd, white, red, green)
+    sd.box(translate(-0.33, -0.4, -0.3) @ rotate("y", 17) @ scale(0.3, 0.6, 0.3), white)
+    sd.box(translate(0.33, -0.7, 0.3) @ rotate("y", -17) @ scale(0.3, 0.3, 0.3), white)
+    if quad_light:
+        sd.rectangle(translate(0, 0.995, 0) @ rotate("x", 90) @ scale(0.25), black, radiance=(17.0, 12.0, 4.0))
+    sd.constant_environment((0.9, 1.0, 1.2), sampling_weight=env_weight)
+    sd.set_camera(lookat((0, 0, 3.9), (0, 0, 0), (0, 1, 0)), 39.3077, res, res, filt, 0.5)
+    return sd
+
+
 SCENES = {"cornell_c1": cornell_c1, "cornell_c2": cornell_c2, "glass_sphere": glass_sphere, "door_c3": door_c3,
-          "triangle_soup": triangle_soup, "caustic_c5": caustic_c5, "cornell_point": cornell_point}
+          "triangle_soup": triangle_soup, "caustic_c5": caustic_c5, "cornell_point": cornell_point, "cornell_sky": cornell_sky}

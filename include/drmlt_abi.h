@@ -66,8 +66,9 @@ enum {
 };
 
 enum {
-    DRMLT_EMITTER_AREA = 0,   /* src/emitters/area.cpp  */
-    DRMLT_EMITTER_POINT = 1   /* src/emitters/point.cpp (technique=path only) */
+    DRMLT_EMITTER_AREA = 0,    /* src/emitters/area.cpp  */
+    DRMLT_EMITTER_POINT = 1,   /* src/emitters/point.cpp (technique=path only) */
+    DRMLT_EMITTER_CONSTANT = 2 /* src/emitters/constant.cpp (technique=path only; at most one) */
 };
 
 enum { DRMLT_FILTER_BOX = 0, DRMLT_FILTER_GAUSSIAN = 1 };
@@ -160,15 +161,19 @@ typedef struct drmlt_bsdf {
     float   p[8];
 } drmlt_bsdf;
 
-/* AREA:  `shape` is the index of the shape carrying the emitter, `radiance` its radiance.
- * POINT: `shape` is the index of the light's position in drmlt_scene.points (one emitter per entry), `radiance` its
- *        intensity in W/sr ("intensity", default Spectrum::getD65() = (1, 1, 1) in RGB builds). Sampled as
- *        PointEmitter::sampleDirect (point.cpp:131-151): a delta position, MIS weight 1, never hit by a ray.
+/* AREA:     `shape` is the index of the shape carrying the emitter, `radiance` its radiance.
+ * POINT:    `shape` is the index of the light's position in drmlt_scene.points (one emitter per entry), `radiance` its
+ *           intensity in W/sr ("intensity", default Spectrum::getD65() = (1, 1, 1) in RGB builds). Sampled as
+ *           PointEmitter::sampleDirect (point.cpp:131-151): a delta position, MIS weight 1, never hit by a ray.
+ * CONSTANT: an environment of constant radiance ("radiance", default Spectrum::getD65() = (1, 1, 1)) seen by every ray
+ *           that leaves the scene; `shape` must be -1 and no shape may name it. At most one per scene (scene.cpp:561-564),
+ *           technique=path only (algo=pssmlt included, which runs over it). Sampled as ConstantBackgroundEmitter::sampleDirect
+ *           (constant.cpp:173-214): cosine-weighted about the shading normal, power-heuristic MIS against the BSDF.
  * The emitters' order is the order of the sampling distribution (Scene::m_emitterPDF over the sampling weights). */
 typedef struct drmlt_emitter {
     int32_t type;        /* DRMLT_EMITTER_*                           */
-    int32_t shape;       /* AREA: shape index; POINT: position index  */
-    float   radiance[3]; /* AREA: radiance; POINT: intensity          */
+    int32_t shape;       /* AREA: shape index; POINT: position index; CONSTANT: -1 */
+    float   radiance[3]; /* AREA, CONSTANT: radiance; POINT: intensity          */
     float   sampling_weight; /* Emitter::getSamplingWeight, default 1 */
 } drmlt_emitter;
 

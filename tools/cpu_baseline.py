@@ -94,13 +94,17 @@ def scene_to_xml(pkg, sd, conf, out_dir, name):
             x.append('  <bsdf type="roughconductor" id="b%d"><string name="distribution" value="%s"/><float name="alpha" value="%.7g"/>'
                      '<float name="extEta" value="1"/><spectrum name="eta" value="%.7g, %.7g, %.7g"/><spectrum name="k" value="%.7g, %.7g, %.7g"/>'
                      '<spectrum name="specularReflectance" value="%.7g, %.7g, %.7g"/></bsdf>' % (i, "ggx" if b.p[7] else "beckmann", b.p[0], *list(b.p)[1:7], *b.rgb))
-    # emitters enter Mitsuba's m_emitters (the order of the sampling PMF) in document order: a point light goes out before the
-    # first shape that carries an emitter of a higher index
-    points = [i for i, e in enumerate(sd.emitters) if e.type == abi.EMITTER_POINT]
+    # emitters enter Mitsuba's m_emitters (the order of the sampling PMF) in document order: a point light or the constant
+    # environment goes out before the first shape that carries an emitter of a higher index
+    points = [i for i, e in enumerate(sd.emitters) if e.type in (abi.EMITTER_POINT, abi.EMITTER_CONSTANT)]
 
     def point_lights_before(k):
         while points and points[0] < k:
             e = sd.emitters[points.pop(0)]
+            if e.type == abi.EMITTER_CONSTANT:
+                x.append('  <emitter type="constant"><spectrum name="radiance" value="%.7g, %.7g, %.7g"/>'
+                         '<float name="samplingWeight" value="%.7g"/></emitter>' % (*e.radiance, e.sampling_weight))
+                continue
             x.append('  <emitter type="point"><point name="position" x="%.9g" y="%.9g" z="%.9g"/><spectrum name="intensity" value="%.7g, %.7g, %.7g"/>'
                      '<float name="samplingWeight" value="%.7g"/></emitter>' % (*sd.points[e.shape], *e.radiance, e.sampling_weight))
 
