@@ -1727,7 +1727,7 @@ void launch_mutate(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStrea
         else if (diffuse) hipLaunchKernelGGL((k_mutate_v5<8, true, false>), g5, block, lds, st, P, n_mut, mut_base);
         else hipLaunchKernelGGL((k_mutate_v5<15, true, false>), g5, block, lds, st, P, n_mut, mut_base);
     } else if (P.kernel_variant == 4) { // free-running chains, flattened bookkeeping, queued splats (rows of 33 floats)
-        const size_t qcap = (P.features & 8) || !P.tables_in_lds ? V4_QCAP_BVH : V4_QCAP; // as the kernel variants below
+        const size_t qcap = (P.features & 8) ? V4_QCAP_BVH : V4_QCAP; // as the kernel variants below (QCAP)
         size_t lds = ((D + 2 * D4 + 4) * V4_STRIDE + 32 + 5 * qcap + 3) / 4 * 4 * sizeof(float);
         if (P.tables_in_lds) lds += (size_t) P.n_shade * 64 + (size_t) P.n_bsdfs * 48 + (size_t) P.n_emitters * 32;
         if (getenv("DRMLT_VERBOSE")) fprintf(stderr, "[drmlt] k_mutate_v4: %zu B of LDS per wave\n", lds);
@@ -1743,6 +1743,9 @@ void launch_mutate(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStrea
             else if (!P.bvh_stack16) hipLaunchKernelGGL((k_mutate_v4<15, true, false, false, true>), g4, block, lds, st, P, n_mut, mut_base);
             else if (P.bvh_overflow) hipLaunchKernelGGL((k_mutate_v4<15, true, false, true, true>), g4, block, lds, st, P, n_mut, mut_base);
             else hipLaunchKernelGGL((k_mutate_v4<15, true, false, true>), g4, block, lds, st, P, n_mut, mut_base);
+        } else if ((P.features & 8) == 0) { // brute-force loop, tables too large for LDS (many point lights): the BVH builds below
+            // would traverse a tree the scene does not have -- their resumable traversal reads P.bvh whatever P.use_bvh says
+            hipLaunchKernelGGL((k_mutate_v4<7, false, false>), g4, block, lds, st, P, n_mut, mut_base);
         } else if (!P.bvh_stack16 && P.features == 8) hipLaunchKernelGGL((k_mutate_v4<8, false, false, false, true>), g4, block, lds, st, P, n_mut, mut_base);
         else if (!P.bvh_stack16) hipLaunchKernelGGL((k_mutate_v4<15, false, false, false, true>), g4, block, lds, st, P, n_mut, mut_base);
         else if (P.bvh_overflow) hipLaunchKernelGGL((k_mutate_v4<15, false, false, true, true>), g4, block, lds, st, P, n_mut, mut_base);

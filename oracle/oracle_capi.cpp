@@ -81,6 +81,8 @@ template <typename F> struct Ctx : CtxBase {
         if (in.work_units <= 0) return "work_units must be positive";
         std::string e = scene.load(s);
         if (!e.empty()) return e;
+        // as drmlt_create: the bidirectional techniques (oracle_bidir.hpp) sample area emitters only
+        if ((mmlt || bdpt) && scene.hasPointOrEnv()) return "point lights and environment emitters are supported for technique=path only";
         c.algo = in.algo; c.type = in.type; c.maxDepth = in.max_depth; c.rrDepth = in.rr_depth;
         c.separateDirect = in.direct_samples >= 0;
         c.acceptanceMap = in.acceptance_map != 0; c.timidAfterLarge = in.timid_after_large != 0;

@@ -5,10 +5,12 @@
 //               include/mitsuba/render/triaccel.h:37-158; skdtree.h:340-429
 //   ray query   src/librender/skdtree.cpp:112-142 (closest), :207-226 (shadow)
 //   emitters    src/emitters/area.cpp:111-189; src/librender/shape.cpp:102-127;
-//               src/librender/scene.cpp:879-904,1057-1060; core/pmf.h:109-188
+//               src/librender/scene.cpp:879-904,1057-1060; core/pmf.h:109-188;
+//               src/emitters/point.cpp:131-151 (technique=path only);
+//               src/emitters/constant.cpp:67-92,173-261 (technique=path only; scene.cpp:396-423 for its box)
 //   bsdfs       src/bsdfs/diffuse.cpp:110-149; src/bsdfs/dielectric.cpp:228-333
 //   sensor      src/sensors/perspective.cpp:126-180,271-300
-//   estimator   src/integrators/path/path.cpp:123-321
+//   estimator   src/integrators/path/path.cpp:123-321 (with the environment: :146-153, :253-285)
 //   path eval   src/libbidir/pathsampler.cpp:529-567 (EUnidirectional)
 // The reference intersects through a SAH kd-tree; for the closest hit the
 // result is the same as testing every primitive, which is what the oracle does.
@@ -55,9 +57,11 @@ template <typename F> struct Shape {
 };
 
 template <typename F> struct Emitter {
-    int shape;
-    V3<F> radiance;
+    int shape;     // area: the shape; point: the position entry; constant: -1
+    V3<F> radiance; // area / constant: radiance; point: intensity
     F weight;
+    int type = DRMLT_EMITTER_AREA;
+    V3<F> pos;     // point: position
 };
 
 template <typename F> struct Intersection {
@@ -99,6 +103,14 @@ public:
     std::vector<Emitter<F>> emitters;
     std::vector<F> emitterCdf; // DiscreteDistribution m_cdf (size n+1)
     V3<F> aabbMin, aabbMax;
+    int envEmitter = -1;       // the constant environment emitter, or -1
+    V3<F> envCenter;           // its bounding sphere (constant.cpp:67-92)
+    F envRadius = 0;
+    bool hasPointOrEnv() const {
+        for (const Emitter<F> &e : emitters)
+            if (e.type != DRMLT_EMITTER_AREA) return true;
+        return false;
+    }
     // camera
     F camToWorld[16];
     F tanHalfFov, aspect, nearClip, farClip;
@@ -182,14 +194,31 @@ public:
             }
             shapes.push_back(sh);
         }
+        // point positions trail `camera`: a struct of the shorter layout has none (drmlt_abi.h)
+        const bool withPoints = s.struct_size >= sizeof(drmlt_scene);
+        const int nPoints = withPoints ? s.n_points : 0;
         emitterCdf.push_back(0);
         for (int i = 0; i < s.n_emitters; ++i) {
             const drmlt_emitter &e = s.emitters[i];
-            if (e.type != DRMLT_EMITTER_AREA) return "unsupported emitter";
-            if (e.shape < 0 || e.shape >= s.n_shapes || shapes[e.shape].emitter != i) return "emitter/shape link mismatch";
-            emitters.push_back({e.shape, V3<F>(e.radiance[0], e.radiance[1], e.radiance[2]), (F) e.sampling_weight});
+            Emitter<F> em{e.shape, V3<F>(e.radiance[0], e.radiance[1], e.radiance[2]), (F) e.sampling_weight, e.type, V3<F>(0)};
+            if (e.type == DRMLT_EMITTER_AREA) {
+                if (e.shape < 0 || e.shape >= s.n_shapes || shapes[e.shape].emitter != i) return "emitter/shape link mismatch";
+            } else if (e.type == DRMLT_EMITTER_POINT) {
+                if (e.shape < 0 || e.shape >= nPoints || !s.points) return "point light: position index out of range";
+                em.pos = V3<F>(s.points[3 * e.shape], s.points[3 * e.shape + 1], s.points[3 * e.shape + 2]);
+            } else if (e.type == DRMLT_EMITTER_CONSTANT) {
+                if (e.shape != -1) return "environment emitter: shape must be -1";
+                if (envEmitter >= 0) return "the scene may only contain one environment emitter";
+                envEmitter = i;
+            } else {
+                return "unsupported emitter";
+            }
+            emitters.push_back(em);
             emitterCdf.push_back(emitterCdf.back() + (F) e.sampling_weight);
         }
+        for (int i = 0; i < s.n_shapes; ++i)
+            if (shapes[i].emitter >= 0 && (shapes[i].emitter >= s.n_emitters || s.emitters[shapes[i].emitter].type != DRMLT_EMITTER_AREA))
+                return "emitter/shape link mismatch";
         if (emitters.empty()) return "scene has no emitters";
         // the kd-tree's box is slightly enlarged after construction (gkdtree.h:1213-1220,
         // MTS_KD_AABB_EPSILON = 1e-3): needed when geometry lies ON the tight box, as walls do
@@ -199,6 +228,21 @@ public:
             aabbMin = aabbMin - (ext * eps + V3<F>(eps));
             ext = aabbMax - aabbMin;
             aabbMax = aabbMax + (ext * eps + V3<F>(eps));
+        }
+        if (envEmitter >= 0) {
+            // ConstantBackgroundEmitter::createShape (constant.cpp:67-92): Scene::initializeBidirectional (scene.cpp:396-405)
+            // has set the scene's box to the kd-tree's expanded by the sensor's position; AABB::getBSphere takes its centre
+            // and the distance to its max corner, times 1.5, at least Epsilon. In double whatever F is.
+            double lo[3], hi[3], r2 = 0;
+            for (int a = 0; a < 3; ++a) {
+                const double cam = s.camera.to_world[4 * a + 3];
+                lo[a] = std::min((double) aabbMin[a], cam);
+                hi[a] = std::max((double) aabbMax[a], cam);
+                const double c = 0.5 * (lo[a] + hi[a]);
+                envCenter[a] = (F) c;
+                r2 += (hi[a] - c) * (hi[a] - c);
+            }
+            envRadius = (F) std::max((double) Consts<F>::Epsilon, 1.5 * std::sqrt(r2));
         }
         F sum = emitterCdf.back();
         for (size_t i = 1; i < emitterCdf.size(); ++i) emitterCdf[i] *= F(1) / sum; // pmf.h:109-121
@@ -362,6 +406,7 @@ public:
         V3<F> ref, refN, p, n, d;
         F dist = 0, pdf = 0;
         int emitter = -1;
+        bool discrete = false; // dRec.measure == EDiscrete (a point light's sample)
     };
 
     // pmf.h:124-139 sample + :164-170 sampleReuse
@@ -459,20 +504,89 @@ public:
         return sh.invArea * (dRec.dist * dRec.dist) / absDot(dRec.d, dRec.n);
     }
 
+    // BSphere::rayIntersect (util.cpp:447-485 for the quadratic) of the environment's bounding sphere
+    bool envSphereIntersect(const V3<F> &o, const V3<F> &d, F &nearT, F &farT) const {
+        const V3<F> oc = o - envCenter;
+        return solveQuadratic(d.lengthSquared(), 2 * dot(oc, d), oc.lengthSquared() - envRadius * envRadius, nearT, farT);
+    }
+
+    // PointEmitter::sampleDirect (point.cpp:131-146): the position is the light's, the two sample components are drawn but
+    // not used, the density is 1 in the discrete measure and there is no facing test on either side
+    V3<F> pointSampleDirect(const Emitter<F> &em, DirectSample &dRec) const {
+        dRec.p = em.pos;
+        dRec.d = dRec.p - dRec.ref;
+        dRec.dist = dRec.d.length();
+        F invDist = F(1) / dRec.dist;
+        dRec.d *= invDist;
+        dRec.n = V3<F>(0);
+        dRec.pdf = 1;
+        dRec.discrete = true;
+        return em.radiance * (invDist * invDist);
+    }
+
+    // ConstantBackgroundEmitter::sampleDirect (constant.cpp:173-214): cosine-weighted about refN in Frame(refN)
+    // (coordinateSystem, util.cpp:606-616), the uniform sphere when refN is zero; the sample ends on the far side of the
+    // bounding sphere. A sample that roundoff put behind refN keeps its pdf (the shadow ray is still traced) but is worth 0.
+    V3<F> envSampleDirect(const Emitter<F> &em, DirectSample &dRec, F sx, F sy) const {
+        V3<F> d;
+        F pdf;
+        const bool refNZero = dRec.refN.isZero();
+        if (!refNZero) {
+            d = squareToCosineHemisphere(sx, sy);
+            pdf = squareToCosineHemispherePdf(d);
+            d = Frame<F>(dRec.refN).toWorld(d);
+        } else {
+            d = squareToUniformSphere(sx, sy);
+            pdf = F(0.25 * kInvPi);
+        }
+        dRec.pdf = 0;
+        F nearT, farT;
+        if (!envSphereIntersect(dRec.ref, d, nearT, farT)) return V3<F>(0);
+        if (!(nearT < 0 && farT > 0)) return V3<F>(0);
+        dRec.p = dRec.ref + d * farT;
+        dRec.n = normalize(envCenter - dRec.p);
+        dRec.d = d;
+        dRec.dist = farT;
+        dRec.pdf = pdf;
+        if (!refNZero && dot(dRec.d, dRec.refN) <= 0) return V3<F>(0);
+        return em.radiance / pdf;
+    }
+
+    // ConstantBackgroundEmitter::fillDirectSamplingRecord (constant.cpp:246-261): a ray that left the scene ends on the far
+    // side of the bounding sphere. False when its origin is outside the sphere (the reference's "internal error").
+    bool envFill(const Ray<F> &ray, DirectSample &dRec) const {
+        F nearT, farT;
+        if (!envSphereIntersect(ray.o, ray.d, nearT, farT) || nearT > 0 || farT < 0) return false;
+        dRec.p = ray.o + ray.d * farT;
+        dRec.n = normalize(envCenter - dRec.p);
+        dRec.d = ray.d;
+        dRec.dist = farT;
+        dRec.emitter = envEmitter;
+        dRec.discrete = false;
+        return true;
+    }
+
     // scene.cpp:879-904; testVisibility = false is what PathVertex::sampleDirect asks for (vertex.cpp:1307: the connection
     // edge tests visibility itself)
     V3<F> sampleEmitterDirect(DirectSample &dRec, F sx, F sy, uint64_t *rayCounter, bool testVisibility = true) const {
         F emPdf;
         size_t index = sampleEmitterIndex(sx, emPdf);
         const Emitter<F> &em = emitters[index];
-        const Shape<F> &sh = shapes[em.shape];
-        shapeSampleDirect(sh, dRec, sx, sy);
-        // AreaLight::sampleDirect, area.cpp:164-178
+        dRec.discrete = false;
         V3<F> value(0);
-        if (dot(dRec.d, dRec.refN) >= 0 && dot(dRec.d, dRec.n) < 0 && dRec.pdf != 0) {
-            value = em.radiance / dRec.pdf;
+        if (em.type == DRMLT_EMITTER_POINT) {
+            value = pointSampleDirect(em, dRec);
+        } else if (em.type == DRMLT_EMITTER_CONSTANT) {
+            value = envSampleDirect(em, dRec, sx, sy);
         } else {
-            dRec.pdf = 0;
+            const Shape<F> &sh = shapes[em.shape];
+            shapeSampleDirect(sh, dRec, sx, sy);
+            // AreaLight::sampleDirect, area.cpp:164-178
+            if (dot(dRec.d, dRec.refN) >= 0 && dot(dRec.d, dRec.n) < 0 && dRec.pdf != 0) {
+                value = em.radiance / dRec.pdf;
+            } else {
+                dRec.pdf = 0;
+            }
         }
         if (dRec.pdf != 0) {
             if (testVisibility) {
@@ -487,11 +601,15 @@ public:
         return V3<F>(0);
     }
 
-    // scene.cpp:1057-1060 with area.cpp:180-189, shape.cpp:118-127
+    // scene.cpp:1057-1060 with area.cpp:180-189, shape.cpp:118-127; constant.cpp:216-231 (solid angle); point.cpp:148-150
     F pdfEmitterDirect(const DirectSample &dRec) const {
         const Emitter<F> &em = emitters[dRec.emitter];
         F pdf = 0;
-        if (dot(dRec.d, dRec.refN) >= 0 && dot(dRec.d, dRec.n) < 0)
+        if (em.type == DRMLT_EMITTER_CONSTANT)
+            pdf = !dRec.refN.isZero() ? F(kInvPi) * std::max(F(0), dot(dRec.d, dRec.refN)) : F(0.25 * kInvPi);
+        else if (em.type == DRMLT_EMITTER_POINT)
+            pdf = dRec.discrete ? F(1) : F(0);
+        else if (dot(dRec.d, dRec.refN) >= 0 && dot(dRec.d, dRec.n) < 0)
             pdf = shapePdfDirect(shapes[em.shape], dRec);
         F discrete = emitterCdf[dRec.emitter + 1] - emitterCdf[dRec.emitter];
         return pdf * discrete;
@@ -663,7 +781,7 @@ template <typename F> struct SplatList {
     }
 };
 
-// path.cpp:123-315 (strictNormals=false, hideEmitters=false, minDepth=0, no env map)
+// path.cpp:123-315 (strictNormals=false, hideEmitters=false, minDepth=0, directTracing=false)
 template <typename F>
 inline V3<F> pathLi(const Scene<F> &scene, Ray<F> ray, Sampler<F> &sampler, int maxDepth, int rrDepth,
                     bool excludeDirect, uint64_t *rays) {
@@ -676,7 +794,9 @@ inline V3<F> pathLi(const Scene<F> &scene, Ray<F> ray, Sampler<F> &sampler, int 
     int depth = 1;
     scene.rayIntersect(ray, its, rays);
     while (depth <= maxDepth || maxDepth < 0) {
-        if (!its.valid) break; // no environment emitter
+        // a camera ray that misses: the environment would count only under (directTracing || non_specular), false here
+        // (path.cpp:146-153); later misses end the loop below
+        if (!its.valid) break;
         const Shape<F> &sh = scene.shapes[its.shape];
         const Bsdf<F> &bsdf = scene.bsdfs[sh.bsdf];
         // emitted radiance on a direct hit: requires a prior non-specular scatter (:162-165)
@@ -696,7 +816,9 @@ inline V3<F> pathLi(const Scene<F> &scene, Ray<F> ray, Sampler<F> &sampler, int 
                 V3<F> wo = its.toLocal(dRec.d);
                 V3<F> bsdfVal = scene.bsdfEval(bsdf, its.wi, wo);
                 if (!bsdfVal.isZero()) {
-                    F bsdfPdf = scene.bsdfPdf(bsdf, its.wi, wo);
+                    // an emitter that is not on a surface (a point light) has no BSDF-sampling density: weight 1
+                    // (path.cpp:203-208)
+                    F bsdfPdf = !dRec.discrete ? scene.bsdfPdf(bsdf, its.wi, wo) : F(0);
                     F a = dRec.pdf * dRec.pdf, b = bsdfPdf * bsdfPdf;
                     Li += throughput * value * bsdfVal * (a / (a + b));
                 }
@@ -724,7 +846,11 @@ inline V3<F> pathLi(const Scene<F> &scene, Ray<F> ray, Sampler<F> &sampler, int 
                 hitEmitter = true;
             }
         } else {
-            break;
+            // the environment seen by the BSDF-sampled ray (path.cpp:253-262)
+            if (scene.envEmitter < 0) break;
+            value = scene.emitters[scene.envEmitter].radiance;
+            if (!scene.envFill(ray, dRec)) break;
+            hitEmitter = true;
         }
         throughput *= bsdfWeight;
         eta *= bEta;
@@ -735,7 +861,7 @@ inline V3<F> pathLi(const Scene<F> &scene, Ray<F> ray, Sampler<F> &sampler, int 
                 Li += throughput * value * (a / (a + b));
             }
         }
-        if (!(type & EIndirect)) break;
+        if (!its.valid || !(type & EIndirect)) break; // path.cpp:292-293
         type = EDirect | EIndirect; // ERadianceNoEmission
         if (depth++ >= rrDepth) {
             F q = std::min(throughput.max() * eta * eta, F(0.95));

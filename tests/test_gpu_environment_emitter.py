@@ -106,50 +106,9 @@ def test_sky_pick_probability_enters_the_mis_weights(pkg, native_lib):
 
 
 # ---------------------------------------------------------------- against the oracle: the sky as a closed box of area lights
-R_BOX = 6.0
-
-
-def _boxed(pkg, sd_sky):
-    """The twin the oracle can render: the sky replaced by six inward-facing black rectangles of radiance L that enclose the
-    scene and the camera. A ray that leaves the scene hits the box; under directTracing = false (camera rays and escapes after
-    delta vertices add nothing, in both scenes) the expected f(u) of the two scenes is the same."""
-    sc = pkg.scenes
-    import copy
-    sd = sc.SceneData(sd_sky.name + "_boxed")
-    sd.shapes = [copy.copy(s) for s in sd_sky.shapes]
-    sd.bsdfs = [copy.copy(b) for b in sd_sky.bsdfs]
-    env = [i for i, e in enumerate(sd_sky.emitters) if e.type == pkg.abi.EMITTER_CONSTANT]
-    assert len(env) == 1 and env[0] == len(sd_sky.emitters) - 1
-    sd.emitters = [copy.copy(e) for e in sd_sky.emitters[:-1]]
-    L = tuple(sd_sky.emitters[-1].radiance)
-    black = sd.diffuse(0.0)
-    R = R_BOX
-    faces = [sc.translate(0, -R, 0) @ sc.rotate("x", -90), sc.translate(0, R, 0) @ sc.rotate("x", 90),
-             sc.translate(0, 0, -R), sc.translate(0, 0, R) @ sc.rotate("y", 180),
-             sc.translate(-R, 0, 0) @ sc.rotate("y", 90), sc.translate(R, 0, 0) @ sc.rotate("y", -90)]
-    for m in faces:
-        m = m @ sc.scale(R)
-        n = m[:3, :3] @ np.array([0.0, 0.0, 1.0])
-        assert np.dot(n, -m[:3, 3]) > 0        # faces the inside
-        sd.rectangle(m, black, radiance=L)
-    sd.camera = sd_sky.camera
-    assert np.all(np.abs(np.array(sd.camera.to_world)[[3, 7, 11]]) < R)
-    return sd
-
-
-def _rough_sky(pkg, res=32):
-    sc = pkg.scenes
-    sd = sc.SceneData("rough_sky")
-    white = sd.diffuse(0.725, 0.71, 0.68)
-    red = sd.diffuse(0.63, 0.065, 0.05)
-    green = sd.diffuse(0.14, 0.45, 0.091)
-    copper = sd.roughconductor(alpha=0.2)
-    sd.rectangle(sc.translate(0, -1, 0) @ sc.rotate("x", -90), copper)
-    sc._room(sd, white, red, green, walls=("ceiling", "back", "left", "right"))
-    sd.box(sc.translate(-0.33, -0.4, -0.3) @ sc.rotate("y", 17) @ sc.scale(0.3, 0.6, 0.3), white)
-    sd.constant_environment((1.0, 0.9, 0.8))
-    sd.set_camera(sc.lookat((0, 0, 3.9), (0, 0, 0), (0, 1, 0)), 39.3077, res, res, pkg.abi.FILTER_BOX, 0.5)
-    return sd
+# (an independent check beside test_gpu_emitter_parity.py, where the oracle renders the sky itself: a twin whose sky is six
+# area-light walls, compared in expectation)
+from emitter_scenes import boxed as _boxed, rough_sky as _rough_sky  # noqa: E402
 
 
 def _sky_scene(pkg, name):

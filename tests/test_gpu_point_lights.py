@@ -61,36 +61,8 @@ def test_point_lit_plane_matches_the_closed_form(pkg, native_lib):
     assert np.all(g["rgb"][outside] == 0)
 
 
-def _limit_pair(pkg, name):
-    """(device scene with a point light, oracle scene with a black sphere of radius r in its place whose area emitter has
-    radiance I / (pi r^2), the same emitter index and the same sampling weight). The proxy's own error is first order in r
-    (oracle against oracle on cornell_point, q99 of the relative luminance error: 6.6e-3 at r = 1e-3, 6.0e-4 at 1e-4), so
-    r = 1e-5 leaves the tolerance to the device."""
-    sc = pkg.scenes
-    r = 1e-5
-
-    def build(point):
-        if name == "cornell_point":
-            sd = sc.cornell_point(32, quad_light=True, point_weight=3.0)
-            pos, inten, w = sd.points[0], tuple(sd.emitters[1].radiance), 3.0
-            if not point:                                          # rebuild without it, then the proxy as emitter 1
-                sd = sc.cornell_c2(32)
-        elif name == "door":
-            sd = sc.door_c3(32)
-            pos, inten, w = (0.4, 0.3, 0.4), (1.5, 1.2, 0.8), 1.0
-        else:
-            sd = sc.triangle_soup(2000, 32)
-            pos, inten, w = (0.1, 0.8, 0.2), (3.0, 2.5, 2.0), 2.0
-        if point:
-            if name != "cornell_point":
-                sd.point_light(pos, intensity=inten, sampling_weight=w)
-        else:
-            black = sd.diffuse(0.0)
-            sd.sphere(pos, r, black, radiance=tuple(v / (np.pi * r * r) for v in inten))
-            sd.emitters[-1].sampling_weight = w
-        return sd
-
-    return build(True), build(False)
+# (an independent check beside test_gpu_emitter_parity.py, where the oracle renders the point light itself)
+from emitter_scenes import limit_pair as _limit_pair  # noqa: E402
 
 
 @pytest.mark.parametrize("name", ["cornell_point", "door", "soup"])
