@@ -7,7 +7,6 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <cstdlib>
 #include <vector>
 
 struct PrimBounds {
@@ -143,14 +142,15 @@ struct Builder {
 } // namespace bvh_detail
 
 // nodes[0] is the root; returns the number of depth-bounded (median) splits. `order[i]` = original index of the primitive stored in slot i.
-inline int build_bvh(const std::vector<PrimBounds> &pb, std::vector<DBvhNode> &nodes, std::vector<int> &order, int max_depth = BVH_STACK) {
+// `leaf_max`: primitives per leaf (DRMLT_BVH_LEAF), clamped to [1, kLeafCap].
+inline int build_bvh(const std::vector<PrimBounds> &pb, std::vector<DBvhNode> &nodes, std::vector<int> &order, int max_depth = BVH_STACK, int leaf_max = bvh_detail::kLeafMax) {
     using namespace bvh_detail;
     const int n = (int) pb.size();
     order.resize(n);
     for (int i = 0; i < n; ++i) order[i] = i;
     nodes.clear();
     Builder b{pb, order, nodes};
-    if (const char *t = getenv("DRMLT_BVH_LEAF")) b.leaf_max = std::max(1, std::min(kLeafCap, atoi(t)));
+    b.leaf_max = std::max(1, std::min(kLeafCap, leaf_max));
     b.max_depth = std::max(std::min(max_depth, kMaxBinaryDepth), median_depth(n, b.leaf_max)); // never below what a balanced tree needs
     if (n <= b.leaf_max) {
         // single leaf under a root whose second child is empty

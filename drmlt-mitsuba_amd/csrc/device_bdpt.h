@@ -24,6 +24,7 @@
 //                taking the cells its own subpaths reach -- ran 44 grid iterations per evaluation with 17 of 64 lanes in each.
 #pragma once
 #include "device_bidir.h"
+#include "launch_plan.h"
 
 enum { BR_P = 0, BR_N = 3, BR_S = 6, BR_WI = 9, BR_LEN2 = 12, BR_COS = 13, BR_GINV = 14, BR_IDS = 15, BR_THR = 16, BR_SHADE = 19, BR_FLOATS = 20 };
 #define BDPT_MAX_BSDFS 4096      // BR_IDS: kind | bsdf << 4 | (emitter + 1) << 16 (drmlt_create refuses scenes beyond these for technique=bdpt)
@@ -52,8 +53,7 @@ __host__ __device__ inline int bdpt_max_dim(int max_depth, int rr_depth) { // ps
     int d = (max_depth + 2) * (2 + (rr_depth < max_depth ? 1 : 0));
     return d + (d & 1);
 }
-// LDS floats of an evaluation beside the sampler rows: the two density row groups and the 64 segment heads of a connection round
-__host__ __device__ inline int bdpt_eval_lds_floats(int max_depth) { return (2 * (2 * max_depth + 1) + 1) * 64; }
+// (bdpt_eval_lds_floats, the LDS floats of an evaluation beside the sampler rows: launch_plan.h)
 
 struct BdptResult {
     float lum;

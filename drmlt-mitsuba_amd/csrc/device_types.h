@@ -124,9 +124,9 @@ struct DParams {
     unsigned long long *stats; // 18 counters, layout of drmlt_stats
     int32_t *error_flag;
     int32_t debug;          // DRMLT_DEBUG bit mask (diagnostics only)
-    int32_t kernel_variant; // 1: k_mutate (nested loops), 2: k_mutate_v2 (lane state machines), 3: k_mutate_v3 (2 lanes per chain), 4: k_mutate_v4 (free-running, flattened bookkeeping; default)
+    int32_t kernel_variant; // technique=path's chain kernel (launch_plan.h): 3 k_mutate_v3 (cross-check), 4 k_mutate_v4 (lane pairs), 5 k_mutate_v5 (ray pool)
     int32_t features;       // bit 0 rough conductor, bit 1 dielectric, bit 2 what is not a polygon (spheres, point lights, environment), bit 3 BVH traversal needed
-    int32_t mh_batch;       // k_mutate_v2: parked lanes needed before the bookkeeping branch is taken
+    int32_t mh_batch;       // k_mutate_v4 / v5: parked chains needed before the bookkeeping branch is taken
     // technique=mmlt (device_bidir.h)
     int32_t technique;        // DRMLT_TECH_*
     int32_t light_image;      // "lightImage"
@@ -156,7 +156,7 @@ struct DParams {
     int32_t n_flat;              // records [0, n_flat) of `prims` are flat (and mirrored in prims_flat), [n_flat, n_prims) are spheres
     int32_t bvh_leaf_shift;      // 0: one primitive per leaf, ~child = slot; 3: ~child = slot << 3 | count
     int32_t bvh_stack16;         // every stack entry fits a short: k_mutate_v4 runs its 16-bit-stack variant
-    int32_t trace_yield;         // k_mutate_v4 on BVH scenes: a traversal slice ends once this many lanes have finished their ray
+    int32_t trace_yield;         // BVH scenes: a traversal slice (v4) or trace phase (v5) ends once this many lanes have finished their ray
     int32_t *bvh_overflow;       // [entry][lane of the grid]: where a traversal stack that outgrows its LDS column puts its oldest entries, or NULL
     uint32_t bvh_ovf_lanes;      // column count of that area (>= lanes of the launch)
     int32_t trace_vote;          // traversal: the wave tests nodes when 16 * (lanes at a leaf) <= trace_vote * (lanes at a node), leaves otherwise

@@ -22,21 +22,21 @@
 // launchers defined in kernels.hip
 void launch_bootstrap(const DParams &P, uint32_t n, float *lum_out, hipStream_t st);
 void launch_init_chains(const DParams &P, const uint32_t *seed_index, const float *seed_lum, hipStream_t st);
-void launch_mutate(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
-void launch_mutate_pssmlt(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
+void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st); // technique=path, both algorithms
 void launch_eval_paths(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out8, hipStream_t st);
 // technique=mmlt (kernels_mmlt.hip)
-void launch_bootstrap_mmlt(const DParams &P, uint32_t n, float *lum_out, hipStream_t st);
-void launch_init_chains_mmlt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, hipStream_t st);
-void launch_mutate_mmlt(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
-void launch_eval_paths_mmlt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out8, hipStream_t st);
+// (`lds`: ChainPlan::aux_lds)
+void launch_bootstrap_mmlt(const DParams &P, uint32_t n, float *lum_out, size_t lds, hipStream_t st);
+void launch_init_chains_mmlt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, size_t lds, hipStream_t st);
+void launch_mutate_mmlt(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
+void launch_eval_paths_mmlt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out8, size_t lds, hipStream_t st);
 void launch_regroup(const uint32_t *work, const int32_t *depth_or_null, uint32_t n, uint32_t n_mut, uint32_t md, uint32_t *order, uint32_t padded, uint32_t *scratch, hipStream_t st);
 size_t regroup_scratch_words(uint32_t n, uint32_t md);
 // technique=bdpt (kernels_bdpt.hip)
-void launch_bootstrap_bdpt(const DParams &P, uint32_t n, float *lum_out, hipStream_t st);
-void launch_init_chains_bdpt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, hipStream_t st);
-void launch_mutate_bdpt(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
-void launch_eval_lists_bdpt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out, uint32_t stride, hipStream_t st);
+void launch_bootstrap_bdpt(const DParams &P, uint32_t n, float *lum_out, size_t lds, hipStream_t st);
+void launch_init_chains_bdpt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, size_t lds, hipStream_t st);
+void launch_mutate_bdpt(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
+void launch_eval_lists_bdpt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out, uint32_t stride, size_t lds, hipStream_t st);
 void launch_render_pt(const DParams &P, uint64_t n_samples, uint32_t stream, float scale, hipStream_t st);
 
 namespace {
@@ -194,7 +194,7 @@ std::string build_scene(drmlt_ctx *ctx, const drmlt_scene &s, std::vector<DBsdf>
     // ---- merge triangle pairs (a,b,c),(a,c,d) that form a parallelogram into one intersection record.
     // Exact: the hit is attributed to the sub-triangle it falls in, with that triangle's barycentrics and
     // shading record, so every path is the one two separate triangles would give -- at half the tests.
-    if (!getenv("DRMLT_NO_QUAD_MERGE")) {
+    if (!ctx->knobs.no_quad_merge) {
         std::vector<DPrim> merged;
         std::vector<PrimBounds> mb;
         std::vector<QuadGeo> mg;
@@ -447,7 +447,8 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     if (hipSetDevice(device) != hipSuccess) return bail(ctx, "hipSetDevice failed");
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) return bail(ctx, "hipStreamCreate failed");
     ctx->own_stream = true;
-    if (const char *e = getenv("DRMLT_SLICE")) ctx->slice = std::max(1, std::min(32768, atoi(e)));
+    ctx->knobs = read_knobs();
+    const Knobs &K = ctx->knobs;
 
     std::vector<DBsdf> bsdfs;
     std::vector<DEmitter> emitters;
@@ -458,18 +459,15 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
 
     // ---- acceleration structure: brute force over wave-uniform records for tiny scenes, BVH otherwise
     DParams &P = ctx->P;
-    int bvh_threshold = 48;
-    if (const char *t = getenv("DRMLT_BVH_THRESHOLD")) bvh_threshold = atoi(t);
     std::vector<DBvhNode> nodes;   // binary SAH tree (host only)
     std::vector<DBvh4Node> nodes4; // what the kernels traverse
-    P.use_bvh = (int) ctx->prims.size() > bvh_threshold ? 1 : 0;
+    P.use_bvh = (int) ctx->prims.size() > K.bvh_threshold ? 1 : 0;
     if (P.use_bvh) {
         std::vector<int> order;
         // SAH splits wherever they lead (the builder's recursion bound, 64 levels, is far from what a surface-area tree
         // needs): a traversal stack that outgrows its LDS column spills to memory (device_path.h: trav_run)
-        int max_depth = 64;
-        if (const char *t = getenv("DRMLT_BVH_MAX_DEPTH")) max_depth = std::min(max_depth, atoi(t)); // tests: exercise the depth-bounded splits
-        const int median_splits = build_bvh(bounds, nodes, order, max_depth);
+        // (DRMLT_BVH_MAX_DEPTH, tests: exercise the depth-bounded splits)
+        const int median_splits = build_bvh(bounds, nodes, order, K.bvh_max_depth, K.bvh_leaf);
         int leaf_shift = 0;
         const int depth4 = build_bvh4(nodes, nodes4, &leaf_shift);
         P.bvh_leaf_shift = leaf_shift;
@@ -477,14 +475,14 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
         if (nodes4.size() * sizeof(DBvh4Node) >= (1ull << 31) || ctx->prims.size() * sizeof(DPrim) >= (1ull << 31))
             return bail(ctx, "scene too large: the BVH node and primitive arrays must stay below 2 GiB each");
         // 16-bit stack entries when every node index and leaf reference fits (k_mutate_v4: 3 KB of LDS instead of 6)
-        P.bvh_stack16 = (nodes4.size() < 32768 && ((order.size() << leaf_shift) | 7u) < 32768 && !getenv("DRMLT_BVH_STACK32")) ? 1 : 0;
+        P.bvh_stack16 = (nodes4.size() < 32768 && ((order.size() << leaf_shift) | 7u) < 32768 && !K.bvh_stack32) ? 1 : 0;
         // a 4-wide node pushes at most 3 entries, so a node at level l is entered with at most 3 (l - 1) on the stack and
         // 3 * depth4 bound it: up to BVH_STACK that is the LDS column (the branch-free pushes use its spare rows); deeper
         // trees get an overflow area in memory, sized per launch (ensure_overflow)
         ctx->bvh_depth = depth4;
         // (k_mutate_v4 keeps only 11 entries of a 32-bit stack in LDS: those scenes always have the area)
         ctx->ovf_entries = (3 * depth4 > BVH_STACK || !P.bvh_stack16) ? (3 * depth4 + 3 + BVH_SPILL - 1) / BVH_SPILL * BVH_SPILL : 0;
-        if (getenv("DRMLT_VERBOSE")) fprintf(stderr, "[drmlt] BVH: %zu primitives, %zu binary / %zu 4-wide nodes, 4-wide depth %d (stack %d in LDS + %d in memory), %d median splits, %d-bit stack entries\n", order.size(), nodes.size(), nodes4.size(), depth4, BVH_STACK, ctx->ovf_entries, median_splits, P.bvh_stack16 ? 16 : 32);
+        if (K.verbose) fprintf(stderr, "[drmlt] BVH: %zu primitives, %zu binary / %zu 4-wide nodes, 4-wide depth %d (stack %d in LDS + %d in memory), %d median splits, %d-bit stack entries\n", order.size(), nodes.size(), nodes4.size(), depth4, BVH_STACK, ctx->ovf_entries, median_splits, P.bvh_stack16 ? 16 : 32);
         // intersection records go into leaf order; shading records stay where the emitters expect them
         std::vector<DPrim> np(order.size());
         for (size_t i = 0; i < order.size(); ++i) np[i] = ctx->prims[order[i]];
@@ -517,7 +515,7 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     // flat-primitive fast path of the brute-force loop: interleaved records + two sentinels no ray can hit
     // (ld.z = 0, lo.z = 1: t = -inf fails t >= tmin)
     P.prims_flat = nullptr; P.has_plain_tri = 0; P.n_flat = 0; P.n_flat_rec = 0; P.prims_box = nullptr; P.n_box = 0;
-    const bool flat_loop = !P.use_bvh && !getenv("DRMLT_NO_FLAT_LOOP");
+    const bool flat_loop = !P.use_bvh && !K.no_flat_loop;
     for (const DPrim &g : ctx->prims) if (g.type != PRIM_SPHERE) P.n_flat++;
     if (ok && flat_loop) {
         // Faces that bound a parallelepiped -- a `cube`'s six merged triangle pairs, the walls of a room -- become ONE cuboid
@@ -525,7 +523,7 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
         // separate faces (the tests compare the two).
         std::vector<char> in_box((size_t) P.n_flat, 0);
         std::vector<DPrimBox> boxes;
-        if (!getenv("DRMLT_NO_BOX_MERGE")) {
+        if (!K.no_box_merge) {
             std::vector<QuadGeo> fg(geo.begin(), geo.begin() + P.n_flat);
             for (size_t i = 0; i < fg.size(); ++i) // a record's shading index must fit the face half-word
                 if (ctx->prims[i].shade >= 1024 || (ctx->prims[i].type != PRIM_RECTANGLE && ctx->prims[i].type != PRIM_QUAD2)) fg[i].usable = false;
@@ -544,7 +542,7 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
                 }
                 boxes.push_back(b);
             }
-            if (getenv("DRMLT_VERBOSE")) fprintf(stderr, "[drmlt] brute-force loop: %d flat records, %zu of them as the faces of %zu cuboids\n", P.n_flat,
+            if (K.verbose) fprintf(stderr, "[drmlt] brute-force loop: %d flat records, %zu of them as the faces of %zu cuboids\n", P.n_flat,
                                                  (size_t) std::count(in_box.begin(), in_box.end(), 1), boxes.size());
         }
         std::vector<DPrimFlat> flat;
@@ -572,47 +570,10 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     }
     if (!ok) return bail(ctx, "device allocation/upload of the scene failed");
 
-    // ---- derived quantities of DRMLT::render (drmlt.cpp:434-476)
-    const uint64_t budget = (uint64_t) cam.width * cam.height * (uint64_t) cfg->sample_count;
-    int work_units = cfg->work_units;
-    if (work_units <= 0) {
-        // "derived" (workUnits = -1, the default). The reference sizes work units for its CPU scheduler -- 200 000 (path) or
-        // 100 000 (mmlt, bdpt) mutations each, drmlt.cpp:434-444: a few hundred chains for a whole image. A device wants the
-        // count that fills it: 196 608 or 131 072 chains for the path technique's pool kernel (64 per wave, three or two waves per SIMD:
-        // below), 131 072 for bdpt's one-chain-per-lane kernel, 262 144 or -- long renders -- 1 048 576 for mmlt's (two rounds, so that shallow waves make room for the next), but never chains shorter than 64 mutations. An explicit workUnits is
-        // taken as given; drmlt_config.work_units_rule = DRMLT_WORK_UNITS_REFERENCE (adaptor: workUnitsRule=reference) restores the reference's formula.
-        if (cfg->work_units_rule == DRMLT_WORK_UNITS_REFERENCE) {
-            const uint64_t per_unit = (mmlt || bdpt) ? 100000 : 200000;
-            work_units = (int) std::max<uint64_t>(1, (budget + per_unit - 1) / per_unit);
-        } else {
-            // (k_mutate_v5, the ray-pool kernel, carries 64 chains per wave: 131 072 fill the device; it is the path technique's kernel
-            // for all three types -- flat scenes included: 2.15e9 at 131 072 chains against k_mutate_v4's 1.79e9 at 65 536)
-            const bool pool_kernel = !mmlt && !bdpt && cfg->algo != DRMLT_ALGO_PSSMLT && !getenv("DRMLT_KERNEL");
-            // (with its proposal rows in device memory the pool kernel runs a THIRD wave per SIMD, kernels.hip: ROWS_MEM -- 196 608 chains:
-            // traversed scenes, whose node fetches the extra wave covers, + 4 % (2000 triangles) ... + 17 % (50 000, 1 000 000), flat
-            // scenes + 20 % -- measured with a step's components read together)
-            const bool small_tables = ctx->shade.size() * 64 + bsdfs.size() * 48 + emitters.size() * 32 <= 16384; // (= P.tables_in_lds, below)
-            const bool three_waves = pool_kernel && (P.use_bvh || small_tables);
-            // mmlt: MANY rounds of waves, run in depth order -- the kernel holds two 64-chain waves per SIMD (131 072 chains), and the more
-            // waves queue behind them the less of a launch is its tail: 262 144 chains 2.56e9 mutations/s on BASELINE's config 5, 524 288
-            // 2.79e9, 1 048 576 2.91e9, 2 097 152 2.94e9. (bdpt, whose workspace is 2 KB per chain, loses with more than fill the device.)
-            // The price is paid before the first mutation: 50 x maxDepth bootstrap samples per chain (drmlt.cpp:456-473) are 3e8 samples for a
-            // million chains at maxDepth 6 -- 2.3 s of seeding against 0.6 s for 262 144 chains (the resampling table is built on the host).
-            // A render gets the million chains when the 14 % are worth more than that: from 2^35 mutations (12 s of kernel time) up.
-            const uint64_t fill = mmlt ? (budget >= (1ull << 35) ? 1048576 : 262144) : (three_waves ? 196608 : ((bdpt || pool_kernel) ? 131072 : 65536));
-            work_units = (int) std::min<uint64_t>(fill, std::max<uint64_t>(64, budget / 64 / 64 * 64));
-        }
-    }
-    ctx->cfg.work_units = work_units;
-    ctx->n_chains = (uint32_t) work_units;
-
     P.prims = ctx->d_prims.as<DPrim>(); P.shade = ctx->d_shade.as<DShade>(); P.bsdfs = ctx->d_bsdfs.as<DBsdf>();
     P.emitters = ctx->d_emitters.as<DEmitter>(); P.bvh = ctx->d_bvh.as<DBvh4Node>(); P.filter_lut = ctx->d_lut.as<float>();
     P.n_prims = (int) ctx->prims.size(); P.n_shade = (int) ctx->shade.size(); P.n_emitters = (int) emitters.size(); P.n_bvh_nodes = (int) nodes4.size();
     P.n_bsdfs = (int) bsdfs.size();
-    // tables ride in LDS when they are small (Cornell class); 16 KB cap keeps 4+ waves per CU
-    P.tables_in_lds = (ctx->shade.size() * 64 + bsdfs.size() * 48 + emitters.size() * 32 <= 16384) ? 1 : 0;
-    if (const char *t = getenv("DRMLT_TABLES_LDS")) P.tables_in_lds = atoi(t) ? P.tables_in_lds : 0;
     P.box_weight = cam.filter == DRMLT_FILTER_BOX ? lut[0] : 0.f;
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) P.cam[r * 4 + c] = cam.to_world[r * 4 + c];
     P.tan_half_fov = (float) std::tan(0.5 * (double) cam.fov_x_deg * M_PI / 180.0);
@@ -626,7 +587,6 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     P.max_dim = find_max_dim_path(cfg->max_depth, cfg->rr_depth);
     P.eff_dim = std::min(P.max_dim, effective_dim_path(cfg->max_depth, cfg->rr_depth));
     P.p_large = cfg->p_large; P.sigma2 = cfg->scale_second * cfg->sigma;
-    P.n_chains = ctx->n_chains;
     P.kelemen_weights = cfg->kelemen_style_weights; P.kelemen_mutation = cfg->kelemen_style_mutation;
     P.pss_sigma = cfg->sigma; P.luminance_b = 1.f;
     P.technique = cfg->technique; P.light_image = cfg->no_light_image ? 0 : 1; P.fix_emitter_path = cfg->fix_emitter_path;
@@ -649,6 +609,36 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
         P.max_dim = 2 * P.mmlt_dmax + P.bd_Dd;
         P.eff_dim = P.mmlt_S + P.mmlt_E + P.bd_Dd;
     }
+
+    P.debug = ctx->knobs.debug;
+    P.features = 0;
+    for (const DBsdf &b : bsdfs) P.features |= b.type == DRMLT_BSDF_ROUGHCONDUCTOR ? 1 : (b.type == DRMLT_BSDF_DIELECTRIC ? 2 : 0);
+    for (const DPrim &g : ctx->prims) if (g.type == PRIM_SPHERE) P.features |= 4;
+    P.env_emitter = -1;
+    for (int i = 0; i < scene->n_emitters; ++i) {
+        if (scene->emitters[i].type == DRMLT_EMITTER_POINT) P.features |= 4; // what is not a polygon
+        if (scene->emitters[i].type == DRMLT_EMITTER_CONSTANT) P.features |= 4, P.env_emitter = i;
+    }
+    if (P.use_bvh) P.features |= 8;
+    if (K.feat_all) P.features = 15;
+
+    // ---- chain count (workUnits = -1: derive_chains) and the chain kernel's build (launch_plan.h), chosen once
+    PlanInputs in;
+    in.technique = cfg->technique; in.algo = cfg->algo;
+    in.work_units = cfg->work_units; in.work_units_rule = cfg->work_units_rule;
+    in.budget = (uint64_t) cam.width * cam.height * (uint64_t) cfg->sample_count; // drmlt.cpp:434-476
+    in.features = P.features; in.use_bvh = P.use_bvh != 0; in.bvh_stack16 = P.bvh_stack16 != 0; in.bvh_overflow = ctx->ovf_entries > 0;
+    in.n_shade = (uint32_t) P.n_shade; in.n_bsdfs = (uint32_t) P.n_bsdfs; in.n_emitters = (uint32_t) P.n_emitters;
+    in.scene_bytes = P.use_bvh ? (uint64_t) P.n_bvh_nodes * sizeof(DBvh4Node) + ctx->prims.size() * sizeof(DPrim) : 0;
+    in.eff_dim = P.eff_dim; in.max_depth = cfg->max_depth; in.mmlt_S = P.mmlt_S; in.mmlt_E = P.mmlt_E;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) in.cus = prop.multiProcessorCount;
+    ctx->n_chains = derive_chains(in, K);
+    ctx->cfg.work_units = (int) ctx->n_chains;
+    P.n_chains = ctx->n_chains;
+    const ChainPlan &plan = ctx->plan = plan_chains(in, ctx->n_chains, K);
+    P.kernel_variant = plan.kernel_variant; P.tables_in_lds = plan.tables_in_lds; P.small_tables_lds = plan.small_tables_lds;
+    P.mh_batch = plan.mh_batch; P.trace_yield = plan.trace_yield; P.pool_refill = plan.pool_refill; P.trace_vote = plan.trace_vote;
 
     ctx->film_floats = (size_t) cam.width * cam.height * 3;
     const size_t film_bytes = film_alloc_floats(cam.width, cam.height) * sizeof(float); // zero rows behind the film: film_tiles.h
@@ -682,73 +672,14 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     P.cur_r = cur + 3 * (size_t) ctx->n_chains; P.cur_g = cur + 4 * (size_t) ctx->n_chains; P.cur_b = cur + 5 * (size_t) ctx->n_chains;
     P.stats = ctx->d_stats.as<unsigned long long>();
     P.error_flag = ctx->d_err.as<int32_t>();
-    P.debug = 0;
-    if (const char *d = getenv("DRMLT_DEBUG")) P.debug = atoi(d);
-    // chain kernel of technique=path: 4 = k_mutate_v4 (lane pairs, 32 chains per wave), 5 = k_mutate_v5 (ray pool, 64 chains per wave:
-    // the default where it applies, see below), 3 = k_mutate_v3 (the bit-equality cross-check)
-    P.kernel_variant = 5;
-    if (const char *k = getenv("DRMLT_KERNEL")) { int kv = atoi(k); P.kernel_variant = kv == 3 ? 3 : (kv == 5 ? 5 : 4); }
-    P.features = 0;
-    for (const DBsdf &b : bsdfs) P.features |= b.type == DRMLT_BSDF_ROUGHCONDUCTOR ? 1 : (b.type == DRMLT_BSDF_DIELECTRIC ? 2 : 0);
-    for (const DPrim &g : ctx->prims) if (g.type == PRIM_SPHERE) P.features |= 4;
-    P.env_emitter = -1;
-    for (int i = 0; i < scene->n_emitters; ++i) {
-        if (scene->emitters[i].type == DRMLT_EMITTER_POINT) P.features |= 4; // what is not a polygon
-        if (scene->emitters[i].type == DRMLT_EMITTER_CONSTANT) P.features |= 4, P.env_emitter = i;
-    }
-    if (P.use_bvh) P.features |= 8;
-    if (getenv("DRMLT_FEAT_ALL")) P.features = 15;
-    // the ray-pool kernel keeps ONE proposal row group in LDS: Green's reverse move and Mira's ratio, which need x, y and z together,
-    // recompute what is not there from the state in device memory and the addressed stream.
-    // On flat scenes it needs the chains to put two of its 64-chain waves on a SIMD: from 98 304 chains up it is the default
-    // (Cornell: v5 2.15e9 at 131 072 chains, 1.11e9 at 65 536; v4 1.79e9 at 65 536, 1.55e9 at 131 072). BASELINE's config 2 fixes
-    // 65 536 chains and therefore runs k_mutate_v4.
-    const bool v5_forced = getenv("DRMLT_KERNEL") && atoi(getenv("DRMLT_KERNEL")) == 5;
-    if (P.kernel_variant == 5 && !P.use_bvh && !v5_forced && ctx->n_chains < 98304u) P.kernel_variant = 4;
-    // (v5 on the Cornell scene, 131 072 chains: batch 16 1.98e9, 24 2.08e9, 32 2.13e9, 48 1.84e9; on the soup: 8 5.05e8, 16 5.24e8, 32 5.06e8)
-    // A scene whose nodes and records exceed the L2 caches (8 x 4 MB) is traversed against memory latency: the ray pool then wants
-    // SHORT phases -- chains step and refill it as soon as a few rays are done (1 000 000 triangles, 2-step calls: yield x batch
-    // 20 x 16 6.9e7, 12 x 8 7.5e7, 8 x 8 7.7e7, 4 x 8 7.7e7 mutations/s; 50 000 triangles, in the L2s: 2.82e8 / 2.75e8 / 2.61e8)
-    const bool beyond_l2 = P.use_bvh && (size_t) P.n_bvh_nodes * sizeof(DBvh4Node) + ctx->prims.size() * sizeof(DPrim) > (size_t) 32 << 20;
-    // (round 4, with the cuboid records -- a cheaper trace pass moves the balance towards larger batches: v4 on config 2 batch 8 1.99e9, 12 2.02e9,
-    // 14 2.05e9, 16 2.04e9, 20 1.94e9; v5 on the same scene at 131 072 chains 24 2.33e9, 32 2.39e9, 40 2.42e9, 48 2.36e9)
-    P.mh_batch = P.kernel_variant == 5 ? (P.use_bvh ? (beyond_l2 ? 8 : 16) : 40) : (P.kernel_variant == 4 ? (P.use_bvh ? (P.bvh_stack16 ? 6 : 4) : (P.features == 0 ? 14 : 8)) : 32); // v4 / v5: chains run free, the bookkeeping branch fires as soon as a few are parked
-    if (const char *k = getenv("DRMLT_MH_BATCH")) P.mh_batch = std::max(1, std::min(64, atoi(k)));
-    // k_mutate_v5 on traversed scenes with chains for more than two 64-chain waves per SIMD (from 163 840 per GPU): the proposal
-    // rows move from LDS to device memory and the kernel is built for three waves per SIMD (kernels.hip: ROWS_MEM)
     P.rows = nullptr;
-    {
-        int cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        const bool can = P.kernel_variant == 5 && (P.use_bvh || P.tables_in_lds) && !mmlt && !bdpt && cfg->algo != DRMLT_ALGO_PSSMLT;
-        bool rows_mem = can && (uint64_t) ctx->n_chains * 2u >= (uint64_t) cus * 4u * 64u * 5u;
-        if (const char *e = getenv("DRMLT_ROWS_MEM")) rows_mem = atoi(e) != 0 && can;
-        if (rows_mem) {
-            if (ctx->d_rows.alloc((size_t) P.eff_dim * ctx->n_chains * sizeof(float)) != hipSuccess) return bail(ctx, "device allocation of the proposal rows failed");
-            P.rows = ctx->d_rows.as<float>();
-        }
-    }
-    // k_mutate_v5 on traversed scenes: room for the small tables beside the pool? LDS per wave without them: 20 480 B in the builds with
-    // 32-bit stacks and rows in LDS (none), 19.5 KB with 16-bit stacks, 11.5 / 10.8 KB with the rows in device memory (twelve waves per CU: 13 KB)
-    {
-        const size_t small = ((size_t) P.n_bsdfs * 12 + (size_t) P.n_emitters * 24) * sizeof(float);
-        const size_t room = P.rows ? (P.bvh_stack16 ? 1536 : 1024) : (P.bvh_stack16 ? 768 : 0);
-        P.small_tables_lds = (P.use_bvh && P.kernel_variant == 5 && small <= room && !getenv("DRMLT_NO_SMALL_TABLES")) ? 1 : 0;
+    if (plan.rows_mem) {
+        if (ctx->d_rows.alloc((size_t) P.eff_dim * ctx->n_chains * sizeof(float)) != hipSuccess) return bail(ctx, "device allocation of the proposal rows failed");
+        P.rows = ctx->d_rows.as<float>();
     }
     P.bvh_overflow = nullptr; P.bvh_ovf_lanes = 0;
     P.exec_order = nullptr;
-    // measured (5-launch calls) on the 2000-triangle soup: 16 3.69e8, 20 3.80e8, 24 3.84e8, 28 3.84e8 mutations/s; on 50 000 triangles (32-bit
-    // stacks, longer traversals): 20 1.90e8, 24 1.86e8, 28 1.79e8; bookkeeping batch there 4 1.89e8, 6 1.86e8, 8 1.82e8
-    // k_mutate_v5 (131 072 chains, 3-step calls) on the soup: yield x bookkeeping batch -- 12: 4.84 / 5.13 / 5.12e8 (batch 8 / 16 / 28),
-    // 16: 5.08 / 5.37 / 5.20, 20: 5.25 / 5.44 / 5.10, 24: 5.31 / 5.40 / 4.81
-    P.trace_yield = P.kernel_variant == 5 ? (beyond_l2 ? 8 : 20) : (P.bvh_stack16 ? 24 : 20);
-    if (const char *k = getenv("DRMLT_TRACE_YIELD")) P.trace_yield = std::max(0, std::min(64, atoi(k)));
     P.boot_weighted = 0;
-    P.pool_refill = 8; // soup, 131 072 chains: 1 5.38e8, 2 5.41e8, 4 5.43e8, 8 5.45e8, 16 5.37e8 mutations/s
-    if (const char *k = getenv("DRMLT_POOL_REFILL")) P.pool_refill = std::max(1, std::min(64, atoi(k)));
-    P.trace_vote = 10; // measured on the 2000-triangle soup: 16 (plain majority) 2.70e8, 10 2.78e8, 5 2.73e8 mutations/s
-    if (const char *k = getenv("DRMLT_TRACE_VOTE")) P.trace_vote = std::max(1, std::min(1024, atoi(k)));
     if (hipDeviceSynchronize() != hipSuccess) return bail(ctx, "device synchronisation failed after setup");
     return ctx;
 }
@@ -809,8 +740,8 @@ static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint3
     HIP_TRY(ctx, d_lum.alloc((size_t) n * (weighted_seeds ? 2 : 1) * sizeof(float)));
     const bool bdpt = ctx->cfg.technique == DRMLT_TECH_BDPT;
     HIP_TRY(ctx, ensure_overflow(ctx, P, std::max<size_t>(n, 2 * (size_t) P.n_chains_alloc)));
-    if (mmlt) launch_bootstrap_mmlt(P, n, d_lum.as<float>(), ctx->stream);
-    else if (bdpt) launch_bootstrap_bdpt(P, n, d_lum.as<float>(), ctx->stream);
+    if (mmlt) launch_bootstrap_mmlt(P, n, d_lum.as<float>(), ctx->plan.aux_lds, ctx->stream);
+    else if (bdpt) launch_bootstrap_bdpt(P, n, d_lum.as<float>(), ctx->plan.aux_lds, ctx->stream);
     else launch_bootstrap(P, n, d_lum.as<float>(), ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     std::vector<float> lum((size_t) n * (weighted_seeds ? 2 : 1));
@@ -883,7 +814,7 @@ static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint3
     HIP_TRY(ctx, hipMemcpyAsync(d_sl.p, seed_lum.data(), seed_lum.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_err.p, 0, 64, ctx->stream));
     HIP_TRY(ctx, ensure_overflow(ctx, P, 2 * (size_t) P.n_chains_alloc));
-    if (mmlt && !getenv("DRMLT_MMLT_NO_SORT")) {
+    if (mmlt && !ctx->knobs.mmlt_no_sort) {
         // execution order of k_mutate_mmlt: chains sorted by their (fixed) path depth, deepest first, whole waves (kernels_mmlt.hip)
         const uint32_t n = ctx->n_chains, padded = (n + 63u) / 64u * 64u;
         std::vector<uint32_t> order(padded, n);
@@ -895,7 +826,7 @@ static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint3
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // `order` is a local
         ctx->P.exec_order = P.exec_order = ctx->d_order.as<uint32_t>();
     }
-    if (bdpt && !getenv("DRMLT_NO_REGROUP")) { // execution order of k_mutate_bdpt: identity until the first launch has told the chains' work apart (regroup_chains)
+    if (bdpt && !ctx->knobs.no_regroup) { // execution order of k_mutate_bdpt: identity until the first launch has told the chains' work apart (regroup_chains)
         const uint32_t n = ctx->n_chains, padded = (n + 63u) / 64u * 64u;
         std::vector<uint32_t> order(padded, n);
         for (uint32_t j = 0; j < n; ++j) order[j] = j;
@@ -904,8 +835,8 @@ static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint3
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // `order` is a local
         ctx->P.exec_order = P.exec_order = ctx->d_order.as<uint32_t>();
     }
-    if (mmlt) launch_init_chains_mmlt(P, d_si.as<uint32_t>(), d_sl.as<float>(), ctx->stream);
-    else if (bdpt) launch_init_chains_bdpt(P, d_si.as<uint32_t>(), d_sl.as<float>(), ctx->stream);
+    if (mmlt) launch_init_chains_mmlt(P, d_si.as<uint32_t>(), d_sl.as<float>(), ctx->plan.aux_lds, ctx->stream);
+    else if (bdpt) launch_init_chains_bdpt(P, d_si.as<uint32_t>(), d_sl.as<float>(), ctx->plan.aux_lds, ctx->stream);
     else launch_init_chains(P, d_si.as<uint32_t>(), d_sl.as<float>(), ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     int32_t flag = 0;
@@ -938,8 +869,8 @@ int drmlt_bootstrap_luminances(drmlt_ctx *ctx, uint64_t seed, uint32_t stream, u
     DevBuf d_lum;
     HIP_TRY(ctx, d_lum.alloc((size_t) n * sizeof(float)));
     HIP_TRY(ctx, ensure_overflow(ctx, P, std::max<size_t>(n, 2 * (size_t) P.n_chains_alloc)));
-    if (ctx->cfg.technique == DRMLT_TECH_MMLT) launch_bootstrap_mmlt(P, n, d_lum.as<float>(), ctx->stream);
-    else if (ctx->cfg.technique == DRMLT_TECH_BDPT) launch_bootstrap_bdpt(P, n, d_lum.as<float>(), ctx->stream);
+    if (ctx->cfg.technique == DRMLT_TECH_MMLT) launch_bootstrap_mmlt(P, n, d_lum.as<float>(), ctx->plan.aux_lds, ctx->stream);
+    else if (ctx->cfg.technique == DRMLT_TECH_BDPT) launch_bootstrap_bdpt(P, n, d_lum.as<float>(), ctx->plan.aux_lds, ctx->stream);
     else launch_bootstrap(P, n, d_lum.as<float>(), ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out, d_lum.p, (size_t) n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -1034,14 +965,14 @@ int drmlt_set_luminance(drmlt_ctx *ctx, double b) {
 // streams are untouched: the same chains bit for bit, in other lanes. Counting sort, stable: deterministic.
 static int regroup_chains(drmlt_ctx *ctx, uint32_t n_mut) {
     const uint32_t n = ctx->n_chains, padded = (n + 63u) / 64u * 64u, md = ctx->cfg.technique == DRMLT_TECH_MMLT ? (uint32_t) ctx->cfg.max_depth : 1u; // (bdpt: no depth classes)
-    if (!getenv("DRMLT_REGROUP_ON_HOST")) {
+    if (!ctx->knobs.regroup_on_host) {
         // on the device, enqueued behind the launch whose counts it reads (kernels_mmlt.hip: launch_regroup): no copy, no synchronisation
         const size_t words = regroup_scratch_words(n, md);
         if (ctx->d_regroup.bytes < words * sizeof(uint32_t)) HIP_TRY(ctx, ctx->d_regroup.alloc(words * sizeof(uint32_t)));
         launch_regroup(ctx->d_done.as<uint32_t>(), ctx->cfg.technique == DRMLT_TECH_MMLT ? ctx->P.chain_depth : nullptr, n, n_mut, md, ctx->d_order.as<uint32_t>(), padded,
                        ctx->d_regroup.as<uint32_t>(), ctx->stream);
         HIP_TRY(ctx, hipGetLastError());
-        if (!getenv("DRMLT_REGROUP_CHECK")) return DRMLT_OK;
+        if (!ctx->knobs.regroup_check) return DRMLT_OK;
         // test hook: the device's permutation against the host's stable counting sort of the same counts
         std::vector<uint32_t> got(padded), work(n);
         HIP_TRY(ctx, hipMemcpyAsync(got.data(), ctx->d_order.p, (size_t) padded * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -1079,9 +1010,6 @@ static int regroup_chains(drmlt_ctx *ctx, uint32_t n_mut) {
     return DRMLT_OK;
 }
 
-// waves of a chain-kernel launch: k_mutate_v4 carries 32 chains per wave (lane pairs), k_mutate_v5 64
-static uint32_t chain_waves(const drmlt_ctx *ctx) { return ctx->P.kernel_variant == 5 ? (ctx->n_chains + 63u) / 64u : (ctx->n_chains + 31u) / 32u; }
-
 int drmlt_run(drmlt_ctx *ctx, uint64_t total_mutations, volatile int *stop, drmlt_progress_cb cb, void *user) {
     if (!ctx) return DRMLT_E_INVALID;
     if (!ctx->seeded) return ctx->fail(DRMLT_E_STATE, "drmlt_run called before drmlt_seed");
@@ -1098,10 +1026,11 @@ int drmlt_run(drmlt_ctx *ctx, uint64_t total_mutations, volatile int *stop, drml
     // chains that are there keep going -- towards the total of THIS call, at most 8192 mutations beyond the target (16-bit event
     // counters per chain and launch). The last launch has target = limit = total: every chain ends at exactly its count.
     // (A single launch has target = limit and is the plain fixed-count launch; the per-chain counts are kept either way.)
-    const bool ahead = ctx->cfg.technique == DRMLT_TECH_PATH && ctx->cfg.algo != DRMLT_ALGO_PSSMLT && ctx->P.kernel_variant >= 4 &&
-                       !getenv("DRMLT_NO_RUN_AHEAD");
+    const Knobs &K = ctx->knobs;
+    const ChainPlan &plan = ctx->plan;
+    const bool ahead = plan.run_ahead;
     const uint64_t call_base = ctx->mutation_base, call_end = call_base + per_chain;
-    const bool regroup = (ctx->cfg.technique == DRMLT_TECH_MMLT || ctx->cfg.technique == DRMLT_TECH_BDPT) && ctx->cfg.algo != DRMLT_ALGO_PSSMLT && ctx->P.exec_order && !getenv("DRMLT_NO_REGROUP");
+    const bool regroup = (ctx->cfg.technique == DRMLT_TECH_MMLT || ctx->cfg.technique == DRMLT_TECH_BDPT) && ctx->cfg.algo != DRMLT_ALGO_PSSMLT && ctx->P.exec_order && !K.no_regroup;
     int since_regroup = 0;
     while (done < per_chain) {
         if (stop && *stop) { rc = DRMLT_E_CANCELLED; break; }
@@ -1110,9 +1039,8 @@ int drmlt_run(drmlt_ctx *ctx, uint64_t total_mutations, volatile int *stop, drml
         // (regrouping: a short first launch -- an eighth of the call, 32 to 256 mutations -- to learn which chains are parked;
         // DRMLT_REGROUP_FIRST overrides its length, clamped to [1, slice]: a launch beyond 32 768 mutations would overflow the
         // kernels' 16-bit event counters)
-        uint64_t first_len = std::max<uint64_t>(32, std::min<uint64_t>(256, per_chain / 8));
-        if (const char *e = getenv("DRMLT_REGROUP_FIRST")) first_len = (uint64_t) std::max(1, std::min(ctx->slice, atoi(e)));
-        const uint64_t slice = (stop || cb || timed) ? std::min(ctx->slice, 256) : (regroup && !ctx->regrouped ? std::min<uint64_t>(ctx->slice, first_len) : (uint64_t) ctx->slice);
+        const uint64_t first_len = K.regroup_first ? (uint64_t) K.regroup_first : std::max<uint64_t>(32, std::min<uint64_t>(256, per_chain / 8));
+        const uint64_t slice = (stop || cb || timed) ? std::min(K.slice, 256) : (regroup && !ctx->regrouped ? std::min<uint64_t>(K.slice, first_len) : (uint64_t) K.slice);
         uint32_t n = (uint32_t) std::min<uint64_t>(slice, per_chain - done);
         evs.emplace_back();
         EventPair &ev = evs.back();
@@ -1120,25 +1048,20 @@ int drmlt_run(drmlt_ctx *ctx, uint64_t total_mutations, volatile int *stop, drml
         HIP_TRY(ctx, hipEventRecord(ev.a, ctx->stream));
         ctx->P.luminance_b = (float) ctx->b;
         HIP_TRY(ctx, ensure_overflow(ctx, ctx->P, 2 * (size_t) ctx->P.n_chains_alloc + 128));
-        if (ctx->cfg.algo == DRMLT_ALGO_PSSMLT) launch_mutate_pssmlt(ctx->P, n, ctx->mutation_base, ctx->stream);
-        else if (ctx->cfg.technique == DRMLT_TECH_MMLT) {
+        if (ctx->cfg.technique != DRMLT_TECH_PATH) {
             DParams Q = ctx->P;
             if (regroup) Q.chain_done = ctx->d_done.as<uint32_t>(); // per-chain evaluation counts of this launch
-            launch_mutate_mmlt(Q, n, ctx->mutation_base, ctx->stream);
-        }
-        else if (ctx->cfg.technique == DRMLT_TECH_BDPT) {
-            DParams Q = ctx->P;
-            if (regroup) Q.chain_done = ctx->d_done.as<uint32_t>(); // per-chain evaluation counts of this launch
-            launch_mutate_bdpt(Q, n, ctx->mutation_base, ctx->stream);
+            if (ctx->cfg.technique == DRMLT_TECH_MMLT) launch_mutate_mmlt(plan, Q, n, ctx->mutation_base, ctx->stream);
+            else launch_mutate_bdpt(plan, Q, n, ctx->mutation_base, ctx->stream);
         }
         else if (ahead) {
             DParams Q = ctx->P;
             const uint64_t target = call_base + done + n;
             Q.chain_done = ctx->d_done.as<uint32_t>();
-            Q.run_limit = (uint32_t) std::min<uint64_t>(call_end, target + (getenv("DRMLT_AHEAD_CAP") ? (uint64_t) atoi(getenv("DRMLT_AHEAD_CAP")) : std::min<uint64_t>(8 * slice, 8192))); // at most eight launches ahead (the per-chain event counters of a launch are 16 bits wide); measured on config 3: 1024 6.7e8, 4096 7.1e8, 8192 7.14e8
-            launch_set_u32(Q.waves_left, chain_waves(ctx), ctx->stream);
-            launch_mutate(Q, (uint32_t) target, 0u, ctx->stream);
-        } else launch_mutate(ctx->P, n, ctx->mutation_base, ctx->stream);
+            Q.run_limit = (uint32_t) std::min<uint64_t>(call_end, target + (K.ahead_cap >= 0 ? (uint64_t) K.ahead_cap : std::min<uint64_t>(8 * slice, 8192))); // at most eight launches ahead (the per-chain event counters of a launch are 16 bits wide); measured on config 3: 1024 6.7e8, 4096 7.1e8, 8192 7.14e8
+            launch_set_u32(Q.waves_left, plan.grid, ctx->stream);
+            launch_mutate(plan, Q, (uint32_t) target, 0u, ctx->stream);
+        } else launch_mutate(plan, ctx->P, n, ctx->mutation_base, ctx->stream);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipEventRecord(ev.b, ctx->stream));
         ctx->mutation_base += n;
@@ -1148,7 +1071,7 @@ int drmlt_run(drmlt_ctx *ctx, uint64_t total_mutations, volatile int *stop, drml
         // sorted on the host -- a D2H copy, an H2D copy and two stream synchronisations per launch; that path survives behind
         // DRMLT_REGROUP_ON_HOST as the cross-check and is thinned to every fourth launch when somebody is watching.) A failure
         // ends the loop through the normal exit below: counters and timings are kept.
-        if (regroup && (!(stop || cb || timed) || !ctx->regrouped || !getenv("DRMLT_REGROUP_ON_HOST") || ++since_regroup >= 4)) {
+        if (regroup && (!(stop || cb || timed) || !ctx->regrouped || !K.regroup_on_host || ++since_regroup >= 4)) {
             rc = regroup_chains(ctx, n);
             if (rc != DRMLT_OK) break;
             ctx->regrouped = true;
@@ -1177,8 +1100,8 @@ int drmlt_run(drmlt_ctx *ctx, uint64_t total_mutations, volatile int *stop, drml
             DParams Q = ctx->P;
             Q.chain_done = ctx->d_done.as<uint32_t>();
             Q.run_limit = top;
-            launch_set_u32(Q.waves_left, chain_waves(ctx), ctx->stream);
-            launch_mutate(Q, top, 0u, ctx->stream);
+            launch_set_u32(Q.waves_left, plan.grid, ctx->stream);
+            launch_mutate(plan, Q, top, 0u, ctx->stream);
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             done += top - ctx->mutation_base;
@@ -1242,7 +1165,7 @@ int drmlt_stats_get(drmlt_ctx *ctx, drmlt_stats *o) {
                 v[16], v[17], v[18], v[19], v[20], v[21]),
         fprintf(stderr, "[drmlt stamps] mh sections: decide+splat %llu commit %llu start %llu fill %llu\n", v[22], v[23], v[24], v[25]),
         fprintf(stderr, "[drmlt stamps] iterations by chains tracing (of 32): 0: %llu, 1-4: %llu, 5-8: %llu, 9-16: %llu, 17-24: %llu, 25-32: %llu\n", v[26], v[27], v[28], v[29], v[30], v[31]);
-    if (getenv("DRMLT_VERBOSE") && v[12])
+    if (ctx->knobs.verbose && v[12])
         fprintf(stderr, "[drmlt bvh] wave iterations: inner %llu (%.1f lanes each), leaf %llu (%.1f lanes each)\n", v[12], (double) v[10] / (double) v[12], v[13],
                 v[13] ? (double) v[11] / (double) v[13] : 0.0);
     if ((ctx->P.debug & 1024) && v[20] && ctx->P.kernel_variant != 5)
@@ -1297,7 +1220,7 @@ int drmlt_eval_paths(drmlt_ctx *ctx, const float *u, uint32_t n, uint32_t dim, d
     HIP_TRY(ctx, d_o.alloc((size_t) n * 8 * sizeof(float)));
     HIP_TRY(ctx, hipMemcpyAsync(d_u.p, u, (size_t) n * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, ensure_overflow(ctx, ctx->P, std::max<size_t>(n, (size_t) ctx->P.n_chains_alloc)));
-    if (mmlt) launch_eval_paths_mmlt(ctx->P, d_u.as<float>(), n, dim, d_o.as<float>(), ctx->stream);
+    if (mmlt) launch_eval_paths_mmlt(ctx->P, d_u.as<float>(), n, dim, d_o.as<float>(), ctx->plan.aux_lds, ctx->stream);
     else launch_eval_paths(ctx->P, d_u.as<float>(), n, dim, d_o.as<float>(), ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     std::vector<float> h((size_t) n * 8);
@@ -1362,7 +1285,7 @@ int drmlt_eval_lists(drmlt_ctx *ctx, const float *u, uint32_t n, uint32_t dim, f
     HIP_TRY(ctx, d_o.alloc((size_t) n * stride * sizeof(float)));
     HIP_TRY(ctx, hipMemcpyAsync(d_u.p, u, (size_t) n * dim * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, ensure_overflow(ctx, ctx->P, (size_t) ctx->P.n_chains_alloc));
-    launch_eval_lists_bdpt(ctx->P, d_u.as<float>(), n, dim, d_o.as<float>(), stride, ctx->stream);
+    launch_eval_lists_bdpt(ctx->P, d_u.as<float>(), n, dim, d_o.as<float>(), stride, ctx->plan.aux_lds, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out, d_o.p, (size_t) n * stride * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -4,6 +4,7 @@
 #include "../../include/drmlt_abi.h"
 #include "device_types.h"
 #include "film_tiles.h" // FILM_PAD_ROWS, film_tile(): the row partition of the tiled exchange
+#include "launch_plan.h"
 
 #include <hip/hip_runtime.h>
 
@@ -57,6 +58,8 @@ struct drmlt_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     DParams P{};
+    Knobs knobs;     // the DRMLT_* environment, read once by drmlt_create
+    ChainPlan plan;  // the chain kernel's build, grid and LDS (launch_plan.h), chosen by drmlt_create
     std::string error;
 
     int bvh_depth = 0;
@@ -78,7 +81,6 @@ struct drmlt_ctx {
     uint64_t host_counters[9] = {0};
     unsigned regroup_checks = 0; // DRMLT_REGROUP_CHECK (test hook): device permutations compared with the host's so far
     bool regrouped = false; // the bidirectional kernels' execution order has been regrouped by work at least once since the last seed (drmlt_capi.cpp: regroup_chains)
-    int slice = 1024; // mutations per chain per launch (<= 32768: the per-lane event counters are 16 bit)
     drmlt_comm *comm = nullptr; // set by drmlt_comm_init / drmlt_node_create
 
     ~drmlt_ctx();

@@ -14,6 +14,7 @@
 #include "device_path.h"
 
 #include "kernel_common.h"
+#include "launch_plan.h" // V4_* / V5_* LDS constants; the launcher below dispatches on its Build
 
 // Bootstrap sample `index` of the replayable stream. ONE compiled body serves k_bootstrap and k_init_chains: the replay is
 // checked for EQUALITY with the bootstrap luminance (drmlt_proc.cpp:509-512), and two inlined copies of the same source
@@ -448,10 +449,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v3(DParams P, uint32_t n
 // same sum. An accepted proposal's weight starts the cumulative weight of the new current state.
 //
 // Chains are the same as k_mutate_v2/v3's (same addressed draws, same arithmetic per chain).
-#define V4_STRIDE 33u // row stride of the sampler rows: (row + chain) mod 32 banks serve per-chain AND per-dimension access patterns
-#define V4_QCAP 160u  // splat queue entries: flushed when a bookkeeping branch (at most 3 x 32 new entries) might not fit
+// (V4_STRIDE, V4_QCAP, V4_QCAP_BVH: launch_plan.h)
 #define V4_STACK32_CAP 11 // LDS entries of a 32-bit traversal stack (the rest spills): 11 + 3 spare rows of 256 B keep eight waves on a CU
-#define V4_QCAP_BVH 100u // BVH scenes: their kernel also keeps the traversal stack in LDS (6 KB); flushes are a negligible part of it
 
 struct V4Lds {
     uint32_t coin_off, list_off, q_off; // float offsets into lds_x
@@ -923,11 +922,9 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
 // ratio need x, y and z together and RECOMPUTE what the rows no longer hold from the state and the addressed stream (Green:
 // v5_iid_second_again, flattened; Mira: PoolRowSampler::y_raw, per deciding lane -- a twentieth of the mutations get that far).
 // Bookkeeping is v4's: decide per lane, commit / proposals / coins flattened over the 64 lanes. Same addressed draws, same arithmetic per component: the same chains.
-#define V5_QCAP 96u        // splat queue entries (a round of the bookkeeping branch adds at most 64: flushed in between)
-#define V5_QCAP_STACK32 0u  // the builds with 32-bit traversal stacks splat straight from the bookkeeping branch: their LDS goes to the stack column
+// (V5_QCAP, V5_QCAP_STACK32, V5_SLOTS, v5_lds_bytes: launch_plan.h)
 #define V5_STACK32_CAP 25 // (no splat queue, coins drawn per lane instead of kept in four rows: 28 rows of 256 B for the column; measured on 50 000 /
                           // 1 000 000 triangles: 11 entries 2.23e8 / 5.65e7, 16 2.48e8 / 7.03e7, 20 2.69e8 / 7.62e7)
-#define V5_SLOTS 128u
 #ifndef V5_ROWS_MEM_WAVES
 #define V5_ROWS_MEM_WAVES 3 // waves per SIMD the ROWS_MEM builds are compiled for (registers) and sized for (LDS)
 #endif
@@ -953,7 +950,6 @@ DEV V5Lds v5_layout(uint32_t D, uint32_t qcap, bool coin_rows) {
     L.status_off = L.ring_off + V5_SLOTS / 4u;
     return L;
 }
-static size_t v5_lds_bytes(uint32_t D, uint32_t qcap, bool coin_rows) { return ((size_t) D * 64u + (coin_rows ? 4u * 64u : 0u) + 64u + 5u * qcap + 8u * V5_SLOTS + 2u * (V5_SLOTS / 4u)) * sizeof(float); } // (+ the scene tables, when they are staged)
 
 // Where a wave's proposal rows live. RowsLds: 64 columns of lds_x (one per chain of the wave). RowsMem: device memory, [dim][chain]
 // beside the state -- the builds that give the rows' 8.7 KB of LDS (and a few registers) for a THIRD wave per SIMD on scenes that
@@ -1685,89 +1681,40 @@ void launch_bootstrap(const DParams &P, uint32_t n, float *lum_out, hipStream_t 
 void launch_init_chains(const DParams &P, const uint32_t *seed_index, const float *seed_lum, hipStream_t st) {
     hipLaunchKernelGGL(k_init_chains, dim3((P.n_chains + 63) / 64), dim3(64), 0, st, P, seed_index, seed_lum);
 }
-void launch_mutate_pssmlt(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st) {
-    hipLaunchKernelGGL(k_mutate_pssmlt, dim3((P.n_chains + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), (size_t) P.eff_dim * 64 * sizeof(float), st, P,
-                       n_mut, mut_base);
-}
-void launch_mutate(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st) {
-    const size_t D = (size_t) P.eff_dim, D4 = (D + 3) & ~(size_t) 3;
-    const dim3 block(CHAIN_BLOCK);
-    if (P.kernel_variant == 5) { // ray pool, 64 chains per wave
-        const bool flat = (P.features & 8) == 0;
-        const bool rows_mem = P.rows != nullptr && (!flat || P.tables_in_lds); // (drmlt_capi.cpp: chains for more than two waves per SIMD)
-        size_t lds = v5_lds_bytes(rows_mem ? 0u : (uint32_t) D, (flat || P.bvh_stack16) ? V5_QCAP : V5_QCAP_STACK32, flat || P.bvh_stack16);
-        if (flat && P.tables_in_lds) lds += (size_t) P.n_shade * 64 + (size_t) P.n_bsdfs * 48 + (size_t) P.n_emitters * 32;
-        if (!flat && P.small_tables_lds) lds += ((size_t) P.n_bsdfs * 12 + (size_t) P.n_emitters * 24) * sizeof(float);
-        if (getenv("DRMLT_VERBOSE")) fprintf(stderr, "[drmlt] k_mutate_v5: %zu B of LDS per wave%s%s\n", lds, flat ? "" : " (+ the traversal stack)", rows_mem ? "; proposal rows in device memory, three waves per SIMD" : "");
-        const dim3 g5((P.n_chains + 63) / 64);
-        const bool diffuse = P.features == 8;
-        if (flat && rows_mem) { // three waves per SIMD, as on traversed scenes
-            if (P.features == 0) hipLaunchKernelGGL((k_mutate_v5<0, true, false, false, true, true>), g5, block, lds, st, P, n_mut, mut_base);
-            else if (P.features == 1) hipLaunchKernelGGL((k_mutate_v5<1, true, false, false, true, true>), g5, block, lds, st, P, n_mut, mut_base);
-            else if ((P.features & ~3) == 0) hipLaunchKernelGGL((k_mutate_v5<3, true, false, false, true, true>), g5, block, lds, st, P, n_mut, mut_base);
-            else hipLaunchKernelGGL((k_mutate_v5<7, true, false, false, true, true>), g5, block, lds, st, P, n_mut, mut_base);
-        }
-        else if (flat) { // brute-force loop as the trace phase; tables in LDS when they are small (they are, for scenes this small)
-            if (!P.tables_in_lds) hipLaunchKernelGGL((k_mutate_v5<7, true, false, false, false>), g5, block, lds, st, P, n_mut, mut_base);
-            else if (P.features == 0 && (P.debug & 128)) hipLaunchKernelGGL((k_mutate_v5<0, true, false, true, true>), g5, block, lds, st, P, n_mut, mut_base); // diagnostic stamps
-            else if (P.features == 0) hipLaunchKernelGGL((k_mutate_v5<0, true, false, false, true>), g5, block, lds, st, P, n_mut, mut_base);
-            else if (P.features == 1) hipLaunchKernelGGL((k_mutate_v5<1, true, false, false, true>), g5, block, lds, st, P, n_mut, mut_base); // rough conductors, no dielectric (config 3)
-            else if ((P.features & ~3) == 0) hipLaunchKernelGGL((k_mutate_v5<3, true, false, false, true>), g5, block, lds, st, P, n_mut, mut_base);
-            else hipLaunchKernelGGL((k_mutate_v5<7, true, false, false, true>), g5, block, lds, st, P, n_mut, mut_base);
-        }
-        else if (rows_mem) {
-            if (!P.bvh_stack16) { if (diffuse) hipLaunchKernelGGL((k_mutate_v5<8, false, true, false, false, true>), g5, block, lds, st, P, n_mut, mut_base); else hipLaunchKernelGGL((k_mutate_v5<15, false, true, false, false, true>), g5, block, lds, st, P, n_mut, mut_base); }
-            else if (P.bvh_overflow) { if (diffuse) hipLaunchKernelGGL((k_mutate_v5<8, true, true, false, false, true>), g5, block, lds, st, P, n_mut, mut_base); else hipLaunchKernelGGL((k_mutate_v5<15, true, true, false, false, true>), g5, block, lds, st, P, n_mut, mut_base); }
-            else if (diffuse) hipLaunchKernelGGL((k_mutate_v5<8, true, false, false, false, true>), g5, block, lds, st, P, n_mut, mut_base);
-            else hipLaunchKernelGGL((k_mutate_v5<15, true, false, false, false, true>), g5, block, lds, st, P, n_mut, mut_base);
-        }
-        else if (!P.bvh_stack16) { if (diffuse) hipLaunchKernelGGL((k_mutate_v5<8, false, true>), g5, block, lds, st, P, n_mut, mut_base); else hipLaunchKernelGGL((k_mutate_v5<15, false, true>), g5, block, lds, st, P, n_mut, mut_base); }
-        else if (P.bvh_overflow) { if (diffuse) hipLaunchKernelGGL((k_mutate_v5<8, true, true>), g5, block, lds, st, P, n_mut, mut_base); else hipLaunchKernelGGL((k_mutate_v5<15, true, true>), g5, block, lds, st, P, n_mut, mut_base); }
-        else if (diffuse && (P.debug & 128)) hipLaunchKernelGGL((k_mutate_v5<8, true, false, true>), g5, block, lds, st, P, n_mut, mut_base); // diagnostic stamps
-        else if (diffuse) hipLaunchKernelGGL((k_mutate_v5<8, true, false>), g5, block, lds, st, P, n_mut, mut_base);
-        else hipLaunchKernelGGL((k_mutate_v5<15, true, false>), g5, block, lds, st, P, n_mut, mut_base);
-    } else if (P.kernel_variant == 4) { // free-running chains, flattened bookkeeping, queued splats (rows of 33 floats)
-        const size_t qcap = (P.features & 8) ? V4_QCAP_BVH : V4_QCAP; // as the kernel variants below (QCAP)
-        size_t lds = ((D + 2 * D4 + 4) * V4_STRIDE + 32 + 5 * qcap + 3) / 4 * 4 * sizeof(float);
-        if (P.tables_in_lds) lds += (size_t) P.n_shade * 64 + (size_t) P.n_bsdfs * 48 + (size_t) P.n_emitters * 32;
-        if (getenv("DRMLT_VERBOSE")) fprintf(stderr, "[drmlt] k_mutate_v4: %zu B of LDS per wave\n", lds);
-        const dim3 g4((P.n_chains + 31) / 32);
-        if (P.tables_in_lds) {
-            if (P.features == 0 && (P.debug & 128)) hipLaunchKernelGGL((k_mutate_v4<0, true, true>), g4, block, lds, st, P, n_mut, mut_base);
-            else if (P.features == 0) hipLaunchKernelGGL((k_mutate_v4<0, true, false>), g4, block, lds, st, P, n_mut, mut_base);
-            else if ((P.features & ~3) == 0 && (P.debug & 128)) hipLaunchKernelGGL((k_mutate_v4<3, true, true>), g4, block, lds, st, P, n_mut, mut_base); // diagnostic stamps
-            else if ((P.features & ~3) == 0) hipLaunchKernelGGL((k_mutate_v4<3, true, false>), g4, block, lds, st, P, n_mut, mut_base);
-            else if ((P.features & 8) == 0) hipLaunchKernelGGL((k_mutate_v4<7, true, false>), g4, block, lds, st, P, n_mut, mut_base);
-            // BVH: 32-bit stacks always run the build with the spill / refill paths (short LDS column), 16-bit stacks only for
-            // trees deeper than their column
-            else if (!P.bvh_stack16) hipLaunchKernelGGL((k_mutate_v4<15, true, false, false, true>), g4, block, lds, st, P, n_mut, mut_base);
-            else if (P.bvh_overflow) hipLaunchKernelGGL((k_mutate_v4<15, true, false, true, true>), g4, block, lds, st, P, n_mut, mut_base);
-            else hipLaunchKernelGGL((k_mutate_v4<15, true, false, true>), g4, block, lds, st, P, n_mut, mut_base);
-        } else if ((P.features & 8) == 0) { // brute-force loop, tables too large for LDS (many point lights): the BVH builds below
-            // would traverse a tree the scene does not have -- their resumable traversal reads P.bvh whatever P.use_bvh says
-            hipLaunchKernelGGL((k_mutate_v4<7, false, false>), g4, block, lds, st, P, n_mut, mut_base);
-        } else if (!P.bvh_stack16 && P.features == 8) hipLaunchKernelGGL((k_mutate_v4<8, false, false, false, true>), g4, block, lds, st, P, n_mut, mut_base);
-        else if (!P.bvh_stack16) hipLaunchKernelGGL((k_mutate_v4<15, false, false, false, true>), g4, block, lds, st, P, n_mut, mut_base);
-        else if (P.bvh_overflow) hipLaunchKernelGGL((k_mutate_v4<15, false, false, true, true>), g4, block, lds, st, P, n_mut, mut_base);
-        else if (P.debug & 128) hipLaunchKernelGGL((k_mutate_v4<15, false, true, true>), g4, block, lds, st, P, n_mut, mut_base); // diagnostic stamps
-        else if (P.features == 8) hipLaunchKernelGGL((k_mutate_v4<8, false, false, true>), g4, block, lds, st, P, n_mut, mut_base); // triangle meshes with diffuse surfaces only
-        else hipLaunchKernelGGL((k_mutate_v4<15, false, false, true>), g4, block, lds, st, P, n_mut, mut_base);
-    } else { // k_mutate_v3, the cross-check: 32 chains per wave, rows of 32 floats
-        size_t lds = (D + 2 * D4) * 32 * sizeof(float);
-        if (P.tables_in_lds) lds += (size_t) P.n_shade * 64 + (size_t) P.n_bsdfs * 48 + (size_t) P.n_emitters * 32;
-        if (getenv("DRMLT_VERBOSE")) fprintf(stderr, "[drmlt] k_mutate_v3: %zu B of LDS per wave\n", lds);
-        // specialisations: 0 = diffuse polygons (Cornell configs); 3 = + rough conductor / dielectric, still flat primitives
-        // under the brute-force loop (door config); 7 = + spheres; 15 = everything (BVH traversal, with its 6 KB LDS stack)
-        const dim3 g3((P.n_chains + 31) / 32);
-        if (P.tables_in_lds) {
-            if (P.features == 0) hipLaunchKernelGGL((k_mutate_v3<0, true>), g3, block, lds, st, P, n_mut, mut_base);
-            else if ((P.features & ~3) == 0) hipLaunchKernelGGL((k_mutate_v3<3, true>), g3, block, lds, st, P, n_mut, mut_base);
-            else if ((P.features & 8) == 0) hipLaunchKernelGGL((k_mutate_v3<7, true>), g3, block, lds, st, P, n_mut, mut_base);
-            else hipLaunchKernelGGL((k_mutate_v3<15, true>), g3, block, lds, st, P, n_mut, mut_base);
-        } else { // large scenes (BVH, tables in HBM/L2): one general variant
-            hipLaunchKernelGGL((k_mutate_v3<15, false>), g3, block, lds, st, P, n_mut, mut_base);
-        }
+// technique=path's chain kernels: the build drmlt_create chose (launch_plan.h: plan_chains), with its grid and LDS
+void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st) {
+    if (plan.verbose && !plan.note.empty()) fprintf(stderr, "%s\n", plan.note.c_str());
+#define LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(plan.grid), dim3(CHAIN_BLOCK), plan.lds, st, P, n_mut, mut_base); break
+    switch (plan.build) {
+    case Build::PSSMLT: LAUNCH(k_mutate_pssmlt);
+    // k_mutate_v5 <FEAT, STACK16, OVF, STAMPS, LDS_TABLES, ROWS_MEM>: ray pool, 64 chains per wave
+    case Build::V5_F0_ROWS: LAUNCH(k_mutate_v5<0, true, false, false, true, true>);   case Build::V5_F1_ROWS: LAUNCH(k_mutate_v5<1, true, false, false, true, true>);
+    case Build::V5_F3_ROWS: LAUNCH(k_mutate_v5<3, true, false, false, true, true>);   case Build::V5_F7_ROWS: LAUNCH(k_mutate_v5<7, true, false, false, true, true>);
+    case Build::V5_F7_GLOBAL: LAUNCH(k_mutate_v5<7, true, false, false, false>);      case Build::V5_F0_STAMPS: LAUNCH(k_mutate_v5<0, true, false, true, true>);
+    case Build::V5_F0: LAUNCH(k_mutate_v5<0, true, false, false, true>);             case Build::V5_F1: LAUNCH(k_mutate_v5<1, true, false, false, true>);
+    case Build::V5_F3: LAUNCH(k_mutate_v5<3, true, false, false, true>);             case Build::V5_F7: LAUNCH(k_mutate_v5<7, true, false, false, true>);
+    case Build::V5_F8_S32_ROWS: LAUNCH(k_mutate_v5<8, false, true, false, false, true>); case Build::V5_F15_S32_ROWS: LAUNCH(k_mutate_v5<15, false, true, false, false, true>);
+    case Build::V5_F8_OVF_ROWS: LAUNCH(k_mutate_v5<8, true, true, false, false, true>);  case Build::V5_F15_OVF_ROWS: LAUNCH(k_mutate_v5<15, true, true, false, false, true>);
+    case Build::V5_F8_ROWS: LAUNCH(k_mutate_v5<8, true, false, false, false, true>);     case Build::V5_F15_ROWS: LAUNCH(k_mutate_v5<15, true, false, false, false, true>);
+    case Build::V5_F8_S32: LAUNCH(k_mutate_v5<8, false, true>); case Build::V5_F15_S32: LAUNCH(k_mutate_v5<15, false, true>);
+    case Build::V5_F8_OVF: LAUNCH(k_mutate_v5<8, true, true>);  case Build::V5_F15_OVF: LAUNCH(k_mutate_v5<15, true, true>);
+    case Build::V5_F8_STAMPS: LAUNCH(k_mutate_v5<8, true, false, true>); case Build::V5_F8: LAUNCH(k_mutate_v5<8, true, false>); case Build::V5_F15: LAUNCH(k_mutate_v5<15, true, false>);
+    // k_mutate_v4 <FEAT, LDS_TABLES, STAMPS, STACK16, OVF>: lane pairs, 32 chains per wave
+    case Build::V4_F0_STAMPS: LAUNCH(k_mutate_v4<0, true, true>); case Build::V4_F0: LAUNCH(k_mutate_v4<0, true, false>);
+    case Build::V4_F3_STAMPS: LAUNCH(k_mutate_v4<3, true, true>); case Build::V4_F3: LAUNCH(k_mutate_v4<3, true, false>); case Build::V4_F7: LAUNCH(k_mutate_v4<7, true, false>);
+    case Build::V4_F15_S32: LAUNCH(k_mutate_v4<15, true, false, false, true>); case Build::V4_F15_OVF: LAUNCH(k_mutate_v4<15, true, false, true, true>);
+    case Build::V4_F15: LAUNCH(k_mutate_v4<15, true, false, true>);            case Build::V4_F7_GLOBAL: LAUNCH(k_mutate_v4<7, false, false>);
+    case Build::V4_F8_S32_GLOBAL: LAUNCH(k_mutate_v4<8, false, false, false, true>); case Build::V4_F15_S32_GLOBAL: LAUNCH(k_mutate_v4<15, false, false, false, true>);
+    case Build::V4_F15_OVF_GLOBAL: LAUNCH(k_mutate_v4<15, false, false, true, true>); case Build::V4_F15_STAMPS_GLOBAL: LAUNCH(k_mutate_v4<15, false, true, true>);
+    case Build::V4_F8_GLOBAL: LAUNCH(k_mutate_v4<8, false, false, true>);            case Build::V4_F15_GLOBAL: LAUNCH(k_mutate_v4<15, false, false, true>);
+    // k_mutate_v3 <FEAT, LDS_TABLES>: the bit-equality cross-check
+    case Build::V3_F0: LAUNCH(k_mutate_v3<0, true>); case Build::V3_F3: LAUNCH(k_mutate_v3<3, true>); case Build::V3_F7: LAUNCH(k_mutate_v3<7, true>);
+    case Build::V3_F15: LAUNCH(k_mutate_v3<15, true>); case Build::V3_F15_GLOBAL: LAUNCH(k_mutate_v3<15, false>);
+    default: // the bidirectional builds: kernels_mmlt.hip, kernels_bdpt.hip (drmlt_run never sends them here)
+        fprintf(stderr, "[drmlt] launch_mutate: build %d is not a technique=path kernel\n", (int) plan.build);
+        abort();
     }
+#undef LAUNCH
 }
 void launch_eval_paths(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out8, hipStream_t st) {
     hipLaunchKernelGGL(k_eval_paths, dim3((n + 63) / 64), dim3(64), 0, st, P, u, n, dim, out8);

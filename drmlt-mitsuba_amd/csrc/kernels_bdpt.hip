@@ -328,29 +328,23 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_eval_lists_bdpt(DParams P, cons
     }
 }
 
-static size_t bdpt_lds_bytes(const DParams &P) {
-    static const size_t pad = getenv("DRMLT_BDPT_LDS_PAD") ? (size_t) atoi(getenv("DRMLT_BDPT_LDS_PAD")) : 0; // diagnostic: occupancy experiments
-    return pad + (((size_t) P.mmlt_S + P.mmlt_E) * 64 + (size_t) bdpt_eval_lds_floats(P.max_depth)) * sizeof(float);
+void launch_bootstrap_bdpt(const DParams &P, uint32_t n, float *lum_out, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(k_bootstrap_bdpt, dim3((P.n_chains_alloc + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), lds, st, P, n, lum_out);
 }
-void launch_bootstrap_bdpt(const DParams &P, uint32_t n, float *lum_out, hipStream_t st) {
-    hipLaunchKernelGGL(k_bootstrap_bdpt, dim3((P.n_chains_alloc + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), bdpt_lds_bytes(P), st, P, n, lum_out);
+void launch_init_chains_bdpt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(k_init_chains_bdpt, dim3((P.n_chains + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), lds, st, P, seed_index, seed_lum);
 }
-void launch_init_chains_bdpt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, hipStream_t st) {
-    hipLaunchKernelGGL(k_init_chains_bdpt, dim3((P.n_chains + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), bdpt_lds_bytes(P), st, P, seed_index,
-                       seed_lum);
+void launch_mutate_bdpt(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st) {
+    const dim3 grid(plan.grid), block(CHAIN_BLOCK);
+    switch (plan.build) {
+    case Build::BDPT_F15: hipLaunchKernelGGL((k_mutate_bdpt<15, 1>), grid, block, plan.lds, st, P, n_mut, mut_base); break;
+    case Build::BDPT_F7_OCC2_TABLES: hipLaunchKernelGGL((k_mutate_bdpt<7, 2, true>), grid, block, plan.lds, st, P, n_mut, mut_base); break;
+    case Build::BDPT_F7_OCC2: hipLaunchKernelGGL((k_mutate_bdpt<7, 2>), grid, block, plan.lds, st, P, n_mut, mut_base); break;
+    case Build::BDPT_F7: hipLaunchKernelGGL((k_mutate_bdpt<7, 1>), grid, block, plan.lds, st, P, n_mut, mut_base); break;
+    default: fprintf(stderr, "[drmlt] launch_mutate_bdpt: build %d is not a technique=bdpt kernel\n", (int) plan.build); abort();
+    }
 }
-void launch_mutate_bdpt(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st) {
-    const dim3 grid((P.n_chains + CHAIN_BLOCK - 1) / CHAIN_BLOCK), block(CHAIN_BLOCK);
-    static const int force_occ = getenv("DRMLT_BDPT_OCC") ? atoi(getenv("DRMLT_BDPT_OCC")) : 0; // diagnostic
-    const bool two = force_occ ? force_occ == 2 : (!P.use_bvh && grid.x > 1024u + 256u && bdpt_lds_bytes(P) <= 20480);
-    const size_t tb = ((size_t) P.n_bsdfs * 12 + (size_t) P.n_emitters * (8 + 16)) * sizeof(float); // BSDFs, emitters, the emitters' shape records
-    static const bool global_tables = getenv("DRMLT_BDPT_TABLES_GLOBAL") != nullptr; // A/B
-    if (P.use_bvh) hipLaunchKernelGGL((k_mutate_bdpt<15, 1>), grid, block, bdpt_lds_bytes(P), st, P, n_mut, mut_base);
-    else if (two && !global_tables && bdpt_lds_bytes(P) + tb <= 20480) hipLaunchKernelGGL((k_mutate_bdpt<7, 2, true>), grid, block, bdpt_lds_bytes(P) + tb, st, P, n_mut, mut_base);
-    else if (two) hipLaunchKernelGGL((k_mutate_bdpt<7, 2>), grid, block, bdpt_lds_bytes(P), st, P, n_mut, mut_base);
-    else hipLaunchKernelGGL((k_mutate_bdpt<7, 1>), grid, block, bdpt_lds_bytes(P), st, P, n_mut, mut_base);
+void launch_eval_lists_bdpt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out, uint32_t stride, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(k_eval_lists_bdpt, dim3((P.n_chains_alloc + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), lds, st, P, u, n, dim, out, stride);
 }
-void launch_eval_lists_bdpt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out, uint32_t stride, hipStream_t st) {
-    hipLaunchKernelGGL(k_eval_lists_bdpt, dim3((P.n_chains_alloc + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), bdpt_lds_bytes(P), st, P, u, n, dim, out,
-                       stride);
-}
+

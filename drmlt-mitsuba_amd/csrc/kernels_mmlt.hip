@@ -8,6 +8,7 @@
 // LDS rows (256 B each, [row][lane]): chain state [0, NX), NX = S + E + 1; then the MIS scratch of eval_mmlt.
 #include "device_bidir.h"
 #include "kernel_common.h"
+#include "launch_plan.h"
 
 DEV uint32_t mmlt_nx(const DParams &P) { return (uint32_t) (P.mmlt_S + P.mmlt_E + 1); }
 
@@ -238,27 +239,23 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_eval_paths_mmlt(DParams P, cons
     o[7] = __int_as_float((int) R.nrays);
 }
 
-static size_t mmlt_lds_bytes(const DParams &P) {
-    return ((size_t) P.mmlt_S + P.mmlt_E + 1 + 3 * ((size_t) P.max_depth + 3)) * 64 * sizeof(float);
+void launch_bootstrap_mmlt(const DParams &P, uint32_t n, float *lum_out, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(k_bootstrap_mmlt, dim3((n + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), lds, st, P, n, lum_out);
 }
-void launch_bootstrap_mmlt(const DParams &P, uint32_t n, float *lum_out, hipStream_t st) {
-    hipLaunchKernelGGL(k_bootstrap_mmlt, dim3((n + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), mmlt_lds_bytes(P), st, P, n, lum_out);
+void launch_init_chains_mmlt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(k_init_chains_mmlt, dim3((P.n_chains + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), lds, st, P, seed_index, seed_lum);
 }
-void launch_init_chains_mmlt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, hipStream_t st) {
-    hipLaunchKernelGGL(k_init_chains_mmlt, dim3((P.n_chains + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), mmlt_lds_bytes(P), st, P,
-                       seed_index, seed_lum);
+void launch_mutate_mmlt(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st) {
+    const dim3 grid(plan.grid), block(CHAIN_BLOCK);
+    switch (plan.build) {
+    case Build::MMLT_F7_TABLES: hipLaunchKernelGGL((k_mutate_mmlt<7, true>), grid, block, plan.lds, st, P, n_mut, mut_base); break;
+    case Build::MMLT_F15: hipLaunchKernelGGL(k_mutate_mmlt<15>, grid, block, plan.lds, st, P, n_mut, mut_base); break;
+    case Build::MMLT_F7: hipLaunchKernelGGL(k_mutate_mmlt<7>, grid, block, plan.lds, st, P, n_mut, mut_base); break;
+    default: fprintf(stderr, "[drmlt] launch_mutate_mmlt: build %d is not a technique=mmlt kernel\n", (int) plan.build); abort();
+    }
 }
-void launch_mutate_mmlt(const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st) {
-    const size_t table_bytes = ((size_t) P.n_shade * 16 + (size_t) P.n_bsdfs * 12 + (size_t) P.n_emitters * 8) * sizeof(float);
-    static const bool no_lds_tables = getenv("DRMLT_MMLT_TABLES_GLOBAL") != nullptr; // A/B
-    if (!P.use_bvh && P.tables_in_lds && !no_lds_tables && mmlt_lds_bytes(P) + table_bytes <= 20480)
-        hipLaunchKernelGGL((k_mutate_mmlt<7, true>), dim3((P.n_chains + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), mmlt_lds_bytes(P) + table_bytes, st, P, n_mut, mut_base);
-    else if (P.use_bvh) hipLaunchKernelGGL(k_mutate_mmlt<15>, dim3((P.n_chains + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), mmlt_lds_bytes(P), st, P, n_mut, mut_base);
-    else hipLaunchKernelGGL(k_mutate_mmlt<7>, dim3((P.n_chains + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), mmlt_lds_bytes(P), st, P, n_mut,
-                       mut_base);
-}
-void launch_eval_paths_mmlt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out8, hipStream_t st) {
-    hipLaunchKernelGGL(k_eval_paths_mmlt, dim3((n + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), mmlt_lds_bytes(P), st, P, u, n, dim, out8);
+void launch_eval_paths_mmlt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out8, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL(k_eval_paths_mmlt, dim3((n + CHAIN_BLOCK - 1) / CHAIN_BLOCK), dim3(CHAIN_BLOCK), lds, st, P, u, n, dim, out8);
 }
 
 
