@@ -261,13 +261,17 @@ DEV void eval_bdpt(const DParams &P, const TablesT &T, MSampler &smp, bool activ
                         const float e = cosThetaT < 0.f ? B.p[0] : B.p[1]; // bRec.eta
                         if (!emitter) eta2 = e * e;
                     }
+                } else if (B.type == 3) { // conductor.cpp:254-290: the mirror direction, discrete pdf 1, eta unchanged
+                    delta = true;
+                    pdf_fwd = 1.f;
+                    w = make_conductor(B).sample(cur.wi, wo);
                 } else {
                     pdf_fwd = 0.f;
                     w = make_rc(B).sample(cur.wi, u0, u1, wo, pdf_fwd);
                 }
                 if (is_zero3(w)) WALK_FAIL;
                 if (cur.wi.z == 0.f || wo.z == 0.f) WALK_FAIL;
-                pdf_rev = delta ? dielectric_pdf_delta(B, wo, cur.wi) : bsdf_pdf_sa(B, wo, cur.wi);
+                pdf_rev = delta ? bsdf_pdf_delta(B, wo, cur.wi) : bsdf_pdf_sa(B, wo, cur.wi);
                 if (!(pdf_rev > 2.93873587705571876e-39f)) WALK_FAIL;
                 d = fma3(cur.s, wo.x, fma3(cross3(cur.n, cur.s), wo.y, cur.n * wo.z));
             }
@@ -323,7 +327,7 @@ DEV void eval_bdpt(const DParams &P, const TablesT &T, MSampler &smp, bool activ
             nv.shade = h.prim;
             {
                 const int bt = T.bsdf(nv.bsdf).type;
-                nv.degenerate = !(bt == 0 || bt == 2 || Sh.emitter >= 0);
+                nv.degenerate = !(bt == 0 || bt == 2 || Sh.emitter >= 0); // delta BSDFs (1, 3) cannot be connected
             }
             nv.wi = to_local(nv, -d);
             nv.e_len2 = len2;

@@ -143,19 +143,22 @@ DEV DRoughConductor make_rc(const DBsdf &B) {
     return DRoughConductor{DMicrofacet{B.p[7] != 0.f, fmaxf(B.p[0], 1e-4f)}, mk3(B.p[1], B.p[2], B.p[3]), mk3(B.p[4], B.p[5], B.p[6]),
                            ld3(B.rgb)};
 }
-// f * |cos wo| under the solid-angle measure (delta BSDFs: 0)
+DEV DConductor make_conductor(const DBsdf &B) {
+    return DConductor{mk3(B.p[1], B.p[2], B.p[3]), mk3(B.p[4], B.p[5], B.p[6]), ld3(B.rgb)};
+}
+// f * |cos wo| under the solid-angle measure (delta BSDFs, types 1 and 3: 0)
 DEV f3 bsdf_eval_sa(const DBsdf &B, f3 wi, f3 wo) {
     if (B.type == 0) {
         if (!(wi.z > 0.f && wo.z > 0.f)) return mk3(0.f, 0.f, 0.f);
         return ld3(B.rgb) * (INV_PI_F * wo.z);
     }
     if (B.type == 2) return make_rc(B).eval(wi, wo);
-    return mk3(0.f, 0.f, 0.f);
+    return mk3(0.f, 0.f, 0.f); // dielectric, smooth conductor
 }
 DEV float bsdf_pdf_sa(const DBsdf &B, f3 wi, f3 wo) {
     if (B.type == 0) return (wi.z > 0.f && wo.z > 0.f) ? INV_PI_F * wo.z : 0.f;
     if (B.type == 2) return make_rc(B).pdf(wi, wo);
-    return 0.f;
+    return 0.f; // dielectric, smooth conductor
 }
 // dielectric.cpp:255-276: discrete-measure pdf of wo given wi
 DEV float dielectric_pdf_delta(const DBsdf &B, f3 wi, f3 wo) {
@@ -168,6 +171,12 @@ DEV float dielectric_pdf_delta(const DBsdf &B, f3 wi, f3 wo) {
     float scale = -(cosThetaT < 0.f ? B.p[1] : B.p[0]);
     if (fabsf(dot3(mk3(scale * wi.x, scale * wi.y, cosThetaT), wo) - 1.f) > 1e-3f) return 0.f;
     return 1.f - F;
+}
+// conductor.cpp:223-252: the same for the mirror -- 1 where wo is the reflection of wi, both on the front side
+DEV float conductor_pdf_delta(f3 wi, f3 wo) { return DConductor::pdf_delta(wi, wo); }
+// discrete-measure pdf of a delta BSDF (type 1 or 3)
+DEV float bsdf_pdf_delta(const DBsdf &B, f3 wi, f3 wo) {
+    return B.type == 1 ? dielectric_pdf_delta(B, wi, wo) : conductor_pdf_delta(wi, wo);
 }
 
 // ------------------------------------------------------------------ sensor helpers
@@ -387,13 +396,17 @@ DEV void eval_mmlt(const DParams &P, const TablesT &T, MSampler &smp, int depth,
                     float factor = sensor ? (cosThetaT < 0.f ? B.p[1] : B.p[0]) : 1.f;
                     w = mk3(factor * factor, factor * factor, factor * factor);
                 }
+            } else if (B.type == 3) { // conductor.cpp:254-290: the mirror direction, discrete pdf 1
+                delta = true;
+                pdf_fwd = 1.f;
+                w = make_conductor(B).sample(cur.wi, wo);
             } else {
                 pdf_fwd = 0.f;
                 w = make_rc(B).sample(cur.wi, u0, u1, wo, pdf_fwd);
             }
             if (is_zero3(w)) WALK_FAIL;
             if (cur.wi.z == 0.f || wo.z == 0.f) WALK_FAIL; // vertex.cpp:206-211 with ng == ns
-            pdf_rev = delta ? dielectric_pdf_delta(B, wo, cur.wi) : bsdf_pdf_sa(B, wo, cur.wi);
+            pdf_rev = delta ? bsdf_pdf_delta(B, wo, cur.wi) : bsdf_pdf_sa(B, wo, cur.wi);
             if (!(pdf_rev > 2.93873587705571876e-39f)) WALK_FAIL; // RCPOVERFLOW, :236-239
             thr = thr * w;
             if (!cur.degenerate && !delta) conn |= 1u << pos;
@@ -439,7 +452,7 @@ DEV void eval_mmlt(const DParams &P, const TablesT &T, MSampler &smp, int depth,
         nv.shade = h.prim;
         {
             const int bt = T.bsdf(nv.bsdf).type;
-            nv.degenerate = !(bt == 0 || bt == 2 || Sh.emitter >= 0); // edge.cpp:66-69
+            nv.degenerate = !(bt == 0 || bt == 2 || Sh.emitter >= 0); // edge.cpp:66-69: delta BSDFs (1, 3) cannot be connected
         }
         nv.wi = to_local(nv, -d);
         nv.e_len2 = len2;

@@ -149,6 +149,27 @@ DEV float fresnel_conductor_exact(float cosThetaI, float eta, float k) {
     return 0.5f * (Rp2 + Rs2);
 }
 
+// Smooth conductor, the perfect mirror (src/bsdfs/conductor.cpp:223-290): rgb = specularReflectance, p[1..3] = eta, p[4..6] = k
+// (the rough conductor's slots). Front side only, one discrete direction; under the solid-angle measure eval and pdf are 0.
+struct DConductor {
+    f3 eta, k, refl;
+    DEV f3 fresnel(float c) const {
+        return mk3(fresnel_conductor_exact(c, eta.x, k.x), fresnel_conductor_exact(c, eta.y, k.y), fresnel_conductor_exact(c, eta.z, k.z)) * refl;
+    }
+    // :254-290: wo = reflect(wi) with discrete pdf 1; the weight is 0 from below the surface. Straight-line: the three
+    // Fresnel terms are evaluated whatever the side and the result is selected.
+    DEV f3 sample(f3 wi, f3 &wo) const {
+        wo = mk3(-wi.x, -wi.y, wi.z);
+        const f3 w = fresnel(wi.z);
+        return wi.z <= 0.f ? mk3(0.f, 0.f, 0.f) : w;
+    }
+    // :223-252, discrete measure: is wo the mirror direction of wi (DeltaEpsilon), both on the front side?
+    DEV static bool mirrored(f3 wi, f3 wo) {
+        return wi.z > 0.f && wo.z > 0.f && fabsf(dot3(mk3(-wi.x, -wi.y, wi.z), wo) - 1.f) <= 1e-3f;
+    }
+    DEV static float pdf_delta(f3 wi, f3 wo) { return mirrored(wi, wo) ? 1.f : 0.f; }
+};
+
 // rgb = specularReflectance, p[0] = alpha, p[1..3] = eta, p[4..6] = k, p[7] != 0: GGX
 struct DRoughConductor {
     DMicrofacet distr;

@@ -1237,7 +1237,7 @@ DEV void path_begin(const DParams &P, PathState &ps, float v0, float v1) {
 //   the shadow ray of the SAME vertex concurrently; `shadow_clear` is the partner's result for the
 //   ray handed over in the previous step (`sr`), so a bounce costs one step instead of two. The
 //   order of the radiance additions is the same in both modes (NEE of vertex i, then MIS of i+1).
-// FEAT: scene features compiled in (bit 0 rough conductor, bit 1 dielectric, bit 2 what is not a polygon: spheres, point
+// FEAT: scene features compiled in (bit 0 rough conductor, bit 1 delta BSDFs: dielectric, smooth conductor, bit 2 what is not a polygon: spheres, point
 // lights and the environment, bit 3 BVH); kernels for
 // plain diffuse polygon scenes (the Cornell configs) carry none of the other code or its registers.
 // HAS_BEGIN = false: the caller starts every path with path_begin itself (k_mutate_v4: in its bookkeeping branch), the
@@ -1344,6 +1344,7 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
         ps.bsdf = S.bsdf & 0xffffff;
         B = T.bsdf(ps.bsdf);
         ps.refn_zero = (FEAT & 2) && B.type == 1; // transmissive / two-sided: DirectSamplingRecord(its) zeroes refN
+        // no light sample at a delta vertex, dielectric or smooth conductor (path.cpp:187, the ESmooth gate)
         want_nee = ps.direct_on && (B.type == 0 || ((FEAT & 1) && B.type == 2));
         need = (want_rr ? 1 : 0) + (want_nee ? 2 : 0) + 2;
     }
@@ -1486,6 +1487,12 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
         ps.bweight = rc.sample(ps.wi, ps.bx, ps.by, wo, ps.bpdf);
         ps.beta_eta = 1.f;
         ps.bdelta = false;
+    } else if ((FEAT & 2) && B.type == 3) { // conductor.cpp:254-290; eta and k from the record the step already holds
+        const DConductor mc{mk3(B.p[1], B.p[2], B.p[3]), mk3(B.p[4], B.p[5], B.p[6]), ld3(B.rgb)};
+        ps.bweight = mc.sample(ps.wi, wo); // zero from below the surface: the path ends at the test that follows
+        ps.bpdf = 1.f;
+        ps.beta_eta = 1.f;
+        ps.bdelta = true;
     } else {
         ps.phase = (DUAL && ps.shadow_pending) ? PH_FLUSH : PH_DONE;
         return;

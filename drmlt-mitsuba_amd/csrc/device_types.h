@@ -125,7 +125,7 @@ struct DParams {
     int32_t *error_flag;
     int32_t debug;          // DRMLT_DEBUG bit mask (diagnostics only)
     int32_t kernel_variant; // technique=path's chain kernel (launch_plan.h): 3 k_mutate_v3 (cross-check), 4 k_mutate_v4 (lane pairs), 5 k_mutate_v5 (ray pool)
-    int32_t features;       // bit 0 rough conductor, bit 1 dielectric, bit 2 what is not a polygon (spheres, point lights, environment), bit 3 BVH traversal needed
+    int32_t features;       // bit 0 rough conductor, bit 1 delta BSDFs (dielectric, smooth conductor), bit 2 what is not a polygon (spheres, point lights, environment), bit 3 BVH traversal needed
     int32_t mh_batch;       // k_mutate_v4 / v5: parked chains needed before the bookkeeping branch is taken
     // technique=mmlt (device_bidir.h)
     int32_t technique;        // DRMLT_TECH_*

@@ -92,6 +92,10 @@ void scene_bsphere(const drmlt_scene &s, const std::vector<PrimBounds> &bounds, 
     radius = (float) std::max(1e-4, 1.5 * std::sqrt(r2)); // Epsilon (single precision builds)
 }
 
+std::string unsupported_bsdf(int type) {
+    return "unsupported BSDF type " + std::to_string(type) + " (supported: diffuse, dielectric, roughconductor, conductor)";
+}
+
 // Flatten the scene into intersection + shading records. Returns "" or an error.
 std::string build_scene(drmlt_ctx *ctx, const drmlt_scene &s, std::vector<DBsdf> &bsdfs, std::vector<DEmitter> &emitters,
                         std::vector<PrimBounds> &bounds, std::vector<QuadGeo> &geo) {
@@ -110,8 +114,10 @@ std::string build_scene(drmlt_ctx *ctx, const drmlt_scene &s, std::vector<DBsdf>
         } else if (in.type == DRMLT_BSDF_ROUGHCONDUCTOR) {
             if (!(in.p[0] > 0.f)) return "roughconductor: alpha must be positive";
             for (int k = 0; k < 8; ++k) b.p[k] = in.p[k];
+        } else if (in.type == DRMLT_BSDF_CONDUCTOR) { // eta, k in the rough conductor's slots; p[0] and p[7] are not read
+            for (int k = 1; k < 7; ++k) b.p[k] = in.p[k];
         } else {
-            return "unsupported BSDF type " + std::to_string(in.type) + " (supported: diffuse, dielectric, roughconductor)";
+            return unsupported_bsdf(in.type);
         }
         bsdfs.push_back(b);
     }
@@ -284,6 +290,24 @@ std::string build_scene(drmlt_ctx *ctx, const drmlt_scene &s, std::vector<DBsdf>
     return "";
 }
 
+// BSDF types and the smooth conductor's parameters (SmoothConductor, conductor.cpp): what drmlt_create refuses before it looks
+// for a device. Returns "" or an error.
+std::string validate_bsdfs(const drmlt_scene &s) {
+    for (int i = 0; i < s.n_bsdfs && s.bsdfs; ++i) {
+        const drmlt_bsdf &b = s.bsdfs[i];
+        if (b.type < DRMLT_BSDF_DIFFUSE || b.type > DRMLT_BSDF_CONDUCTOR)
+            return unsupported_bsdf(b.type);
+        if (b.type != DRMLT_BSDF_CONDUCTOR) continue;
+        const std::string which = "conductor " + std::to_string(i) + ": ";
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(b.rgb[k]) || b.rgb[k] < 0.f) return which + "specularReflectance must be finite and non-negative";
+            if (!std::isfinite(b.p[1 + k]) || b.p[1 + k] < 0.f) return which + "eta must be finite and non-negative";
+            if (!std::isfinite(b.p[4 + k]) || b.p[4 + k] < 0.f) return which + "k must be finite and non-negative";
+        }
+    }
+    return "";
+}
+
 // Emitter types, point lights (PointEmitter, point.cpp) and the environment (ConstantBackgroundEmitter, constant.cpp): what
 // drmlt_create refuses before it looks for a device. Returns "" or an error.
 std::string validate_emitters(const drmlt_scene &s, int technique) {
@@ -430,6 +454,8 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     if (mmlt && cfg->timid_after_large) return bail(nullptr, "timidAfterLarge is not defined for technique=mmlt");
     if (cfg->sample_count <= 0) return bail(nullptr, "sample_count must be positive");
     if (!(cfg->p_large >= 0.f && cfg->p_large <= 1.f)) return bail(nullptr, "pLarge must be in [0,1]");
+    const std::string bsdf_err = validate_bsdfs(*scene);
+    if (!bsdf_err.empty()) return bail(nullptr, bsdf_err);
     const std::string point_err = validate_emitters(*scene, cfg->technique);
     if (!point_err.empty()) return bail(nullptr, point_err);
     const drmlt_camera &cam = scene->camera;
@@ -612,7 +638,7 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
 
     P.debug = ctx->knobs.debug;
     P.features = 0;
-    for (const DBsdf &b : bsdfs) P.features |= b.type == DRMLT_BSDF_ROUGHCONDUCTOR ? 1 : (b.type == DRMLT_BSDF_DIELECTRIC ? 2 : 0);
+    for (const DBsdf &b : bsdfs) P.features |= b.type == DRMLT_BSDF_ROUGHCONDUCTOR ? 1 : ((b.type == DRMLT_BSDF_DIELECTRIC || b.type == DRMLT_BSDF_CONDUCTOR) ? 2 : 0);
     for (const DPrim &g : ctx->prims) if (g.type == PRIM_SPHERE) P.features |= 4;
     P.env_emitter = -1;
     for (int i = 0; i < scene->n_emitters; ++i) {

@@ -277,6 +277,26 @@ private:
         return 0;
     }
 
+    // Complex IOR of a conductor plugin (conductor.cpp:162-178, roughconductor.cpp:176-189) into p[1..3] = eta / extEta and
+    // p[4..6] = k / extEta: the material's measured spectra unless eta / k are given; "none" = perfect mirror
+    static void conductorIOR(const Properties &p, drmlt_bsdf &b) {
+        std::string material = p.getString("material", "Cu");
+        std::transform(material.begin(), material.end(), material.begin(), [](unsigned char c) { return (char) std::tolower(c); });
+        Spectrum intEta, intK;
+        if (material == "none") { intEta = Spectrum(0.0f); intK = Spectrum(1.0f); }
+        else if (!(p.hasProperty("eta") && p.hasProperty("k"))) {
+            ref<FileResolver> fResolver = Thread::getThread()->getFileResolver();
+            intEta.fromContinuousSpectrum(InterpolatedSpectrum(fResolver->resolve("data/ior/" + p.getString("material", "Cu") + ".eta.spd")));
+            intK.fromContinuousSpectrum(InterpolatedSpectrum(fResolver->resolve("data/ior/" + p.getString("material", "Cu") + ".k.spd")));
+        }
+        const Float extEta = lookupIOR(p, "extEta", "air");
+        Float r, g, bl;
+        (p.getSpectrum("eta", intEta) / extEta).toLinearRGB(r, g, bl);
+        b.p[1] = (float) r; b.p[2] = (float) g; b.p[3] = (float) bl;
+        (p.getSpectrum("k", intK) / extEta).toLinearRGB(r, g, bl);
+        b.p[4] = (float) r; b.p[5] = (float) g; b.p[6] = (float) bl;
+    }
+
     int bsdfIndex(const BSDF *bsdf, std::vector<drmlt_bsdf> &bsdfs) {
         const Properties &p = bsdf->getProperties();
         std::string name = bsdf->getClass()->getName();
@@ -309,21 +329,12 @@ private:
             b.p[0] = std::max(b.p[0], 1e-4f);
             if (!p.getBoolean("sampleVisible", true))
                 Log(EError, "roughconductor: sampleVisible=false has no MI355X drmlt implementation");
-            // complex IOR: the material's measured spectra unless eta / k are given; "none" = perfect mirror
-            std::string material = p.getString("material", "Cu");
-            std::transform(material.begin(), material.end(), material.begin(), [](unsigned char c) { return (char) std::tolower(c); });
-            Spectrum intEta, intK;
-            if (material == "none") { intEta = Spectrum(0.0f); intK = Spectrum(1.0f); }
-            else if (!(p.hasProperty("eta") && p.hasProperty("k"))) {
-                ref<FileResolver> fResolver = Thread::getThread()->getFileResolver();
-                intEta.fromContinuousSpectrum(InterpolatedSpectrum(fResolver->resolve("data/ior/" + p.getString("material", "Cu") + ".eta.spd")));
-                intK.fromContinuousSpectrum(InterpolatedSpectrum(fResolver->resolve("data/ior/" + p.getString("material", "Cu") + ".k.spd")));
-            }
-            const Float extEta = lookupIOR(p, "extEta", "air");
-            (p.getSpectrum("eta", intEta) / extEta).toLinearRGB(r, g, bl);
-            b.p[1] = (float) r; b.p[2] = (float) g; b.p[3] = (float) bl;
-            (p.getSpectrum("k", intK) / extEta).toLinearRGB(r, g, bl);
-            b.p[4] = (float) r; b.p[5] = (float) g; b.p[6] = (float) bl;
+            conductorIOR(p, b);
+        } else if (name == "SmoothConductor") { // conductor.cpp:151-290: the perfect mirror
+            b.type = DRMLT_BSDF_CONDUCTOR;
+            p.getSpectrum("specularReflectance", Spectrum(1.0f)).toLinearRGB(r, g, bl);
+            b.rgb[0] = (float) r; b.rgb[1] = (float) g; b.rgb[2] = (float) bl;
+            conductorIOR(p, b);
         } else {
             Log(EError, "BSDF type %s has no MI355X drmlt implementation (refusing rather than approximating)", name.c_str());
         }

@@ -94,6 +94,17 @@ class SceneData:
         self.bsdfs.append(m)
         return len(self.bsdfs) - 1
 
+    def conductor(self, eta=(0.2004, 0.9240, 1.1022), k=(3.9129, 2.4528, 2.1421), specular_reflectance=1.0):
+        """Mitsuba `conductor` (src/bsdfs/conductor.cpp): the perfect mirror with the exact conductor Fresnel term. eta and k
+        are relative to the exterior (already divided by extEta); the defaults are roughconductor's copper."""
+        m = abi.Bsdf()
+        m.type = abi.BSDF_CONDUCTOR
+        m.rgb[:] = specular_reflectance if hasattr(specular_reflectance, "__len__") else (specular_reflectance,) * 3
+        m.p[1], m.p[2], m.p[3] = eta
+        m.p[4], m.p[5], m.p[6] = k
+        self.bsdfs.append(m)
+        return len(self.bsdfs) - 1
+
     # -- shapes
     def _emit(self, radiance):
         e = abi.Emitter()
@@ -281,6 +292,23 @@ def door_c3(res=256, ggx=False):
     return sd
 
 
+def mirror_room(res=256):
+    """door_c3's closed room (no partition) with a smooth copper floor (Mitsuba `conductor`) and the quad light on the ceiling:
+    the walls are seen a second time in the floor, and the floor throws a reflected caustic of the light onto them."""
+    sd = SceneData("mirror_room")
+    white = sd.diffuse(0.725, 0.71, 0.68)
+    red = sd.diffuse(0.63, 0.065, 0.05)
+    green = sd.diffuse(0.14, 0.45, 0.091)
+    black = sd.diffuse(0.0)
+    copper = sd.conductor()
+    sd.rectangle(translate(0, -1, 0) @ rotate("x", -90), copper)                      # floor: polished metal
+    _room(sd, white, red, green, walls=("ceiling", "back", "left", "right"))
+    sd.rectangle(translate(0, 0, 1) @ rotate("y", 180), white)                        # front wall (room is closed)
+    sd.rectangle(translate(0, 0.995, -0.2) @ rotate("x", 90) @ scale(0.25), black, radiance=(17.0, 12.0, 4.0))
+    sd.set_camera(lookat((0, -0.2, 0.95), (0, -0.3, -0.4), (0, 1, 0)), 70.0, res, res, abi.FILTER_BOX, 0.5)
+    return sd
+
+
 def triangle_soup(n_tris=2000, res=128, seed=7):
     """Closed room filled with small random diffuse triangles: a scene large enough that the BVH matters."""
     rng = np.random.default_rng(seed)
@@ -358,5 +386,5 @@ def cornell_sky(res=512, filt=abi.FILTER_BOX, quad_light=False, env_weight=1.0):
     return sd
 
 
-SCENES = {"cornell_c1": cornell_c1, "cornell_c2": cornell_c2, "glass_sphere": glass_sphere, "door_c3": door_c3,
+SCENES = {"cornell_c1": cornell_c1, "cornell_c2": cornell_c2, "glass_sphere": glass_sphere, "door_c3": door_c3, "mirror_room": mirror_room,
           "triangle_soup": triangle_soup, "caustic_c5": caustic_c5, "cornell_point": cornell_point, "cornell_sky": cornell_sky}

@@ -62,7 +62,8 @@ enum { DRMLT_SHAPE_TRIANGLE = 0, DRMLT_SHAPE_RECTANGLE = 1, DRMLT_SHAPE_SPHERE =
 enum {
     DRMLT_BSDF_DIFFUSE = 0,        /* src/bsdfs/diffuse.cpp        */
     DRMLT_BSDF_DIELECTRIC = 1,     /* src/bsdfs/dielectric.cpp     */
-    DRMLT_BSDF_ROUGHCONDUCTOR = 2  /* src/bsdfs/roughconductor.cpp */
+    DRMLT_BSDF_ROUGHCONDUCTOR = 2, /* src/bsdfs/roughconductor.cpp */
+    DRMLT_BSDF_CONDUCTOR = 3       /* src/bsdfs/conductor.cpp      */
 };
 
 enum {
@@ -153,7 +154,10 @@ typedef struct drmlt_shape {
  * DIELECTRIC: p[0]=intIOR p[1]=extIOR, rgb unused (specular refl/trans = 1).
  * ROUGHCONDUCTOR: rgb = specularReflectance, p[0]=alpha, p[1..3]=eta rgb,
  *                 p[4..6]=k rgb, p[7]: 0=beckmann 1=ggx.
- * Any other BSDF plugin (smooth conductor, plastic, ...) is refused by
+ * CONDUCTOR: the perfect mirror (SmoothConductor). rgb = specularReflectance,
+ *            p[1..3]=eta rgb, p[4..6]=k rgb: the rough conductor's slots, both
+ *            already divided by extEta. p[0] and p[7] are ignored.
+ * Any other BSDF plugin (plastic, rough dielectric, ...) is refused by
  * drmlt_create, never approximated. */
 typedef struct drmlt_bsdf {
     int32_t type;

@@ -90,6 +90,10 @@ def scene_to_xml(pkg, sd, conf, out_dir, name):
             x.append('  <bsdf type="diffuse" id="b%d"><spectrum name="reflectance" value="%.7g, %.7g, %.7g"/></bsdf>' % (i, *b.rgb))
         elif b.type == abi.BSDF_DIELECTRIC:
             x.append('  <bsdf type="dielectric" id="b%d"><float name="intIOR" value="%.7g"/><float name="extIOR" value="%.7g"/></bsdf>' % (i, b.p[0], b.p[1]))
+        elif b.type == abi.BSDF_CONDUCTOR:
+            x.append('  <bsdf type="conductor" id="b%d"><float name="extEta" value="1"/><spectrum name="eta" value="%.7g, %.7g, %.7g"/>'
+                     '<spectrum name="k" value="%.7g, %.7g, %.7g"/><spectrum name="specularReflectance" value="%.7g, %.7g, %.7g"/></bsdf>'
+                     % (i, *list(b.p)[1:7], *b.rgb))
         else:
             x.append('  <bsdf type="roughconductor" id="b%d"><string name="distribution" value="%s"/><float name="alpha" value="%.7g"/>'
                      '<float name="extEta" value="1"/><spectrum name="eta" value="%.7g, %.7g, %.7g"/><spectrum name="k" value="%.7g, %.7g, %.7g"/>'
