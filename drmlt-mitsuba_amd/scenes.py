@@ -386,5 +386,17 @@ def cornell_sky(res=512, filt=abi.FILTER_BOX, quad_light=False, env_weight=1.0):
     return sd
 
 
+def deep_chain(res=64, n=160):
+    """C2 plus `n` geometrically shrinking triangles: SAH peels a few of them per level, a chain more than 20 levels deep. A test
+    scene (the traversal stacks' overflow area), not one of SCENES."""
+    sd = cornell_c2(res)
+    white = 0
+    for i in range(n):
+        s = 0.7 * 0.5 ** (i * 0.3)        # down to 2e-15: areas stay representable in fp32
+        x = 0.9 * 0.5 ** (i * 0.3)        # clustered towards the origin, where fp32 keeps resolving them
+        sd.triangle((x, 0.0, 0.0), (x + 0.3 * s, 0.0, 0.0), (x, 0.3 * s, 0.1 * s), white)
+    return sd
+
+
 SCENES = {"cornell_c1": cornell_c1, "cornell_c2": cornell_c2, "glass_sphere": glass_sphere, "door_c3": door_c3, "mirror_room": mirror_room,
           "triangle_soup": triangle_soup, "caustic_c5": caustic_c5, "cornell_point": cornell_point, "cornell_sky": cornell_sky}

@@ -81,12 +81,7 @@ def test_deep_bvh_spills_its_traversal_stack(pkg, ob, native_lib, capfd):
     DRMLT_BVH_MAX_DEPTH bounds the binary depth instead (median-split fallback). Either way the traversal must agree
     with the brute-force loop."""
     import re
-    sd = pkg.scenes.cornell_c2(64)
-    white = 0
-    for i in range(160):
-        s = 0.7 * 0.5 ** (i * 0.3)        # down to 2e-15: areas stay representable in fp32
-        x = 0.9 * 0.5 ** (i * 0.3)        # clustered towards the origin, where fp32 keeps resolving them
-        sd.triangle((x, 0.0, 0.0), (x + 0.3 * s, 0.0, 0.0), (x, 0.3 * s, 0.1 * s), white)
+    sd = pkg.scenes.deep_chain(64)   # shared with tests/test_scene_prep.py
     u = np.random.default_rng(5).random((8192, 50), dtype=np.float32)
     cfg = pkg.abi.make_config(type="orbital", max_depth=8, direct_samples=-1, work_units=64)
     os.environ["DRMLT_BVH_THRESHOLD"] = "1000000"
