@@ -138,6 +138,46 @@ struct MSampler {
     }
 };
 
+// The sampler triple of a bidirectional chain, bootstrap sample or evaluation point. direct_ident: mmlt's direct sampler has
+// identity stages, bdpt's is an ordinary third sampler (MSampler::direct_ident).
+DEV void msampler_setup(MSampler &smp, const DParams &P, uint32_t lane, bool direct_ident) {
+    smp.key0 = P.key0; smp.key1 = P.key1;
+    smp.type = P.type; smp.sigma2 = P.sigma2; smp.large = false;
+    smp.lane = lane; smp.arr = nullptr;
+    smp.S = (uint32_t) P.mmlt_S; smp.E = (uint32_t) P.mmlt_E;
+    smp.base_e = 2u * (uint32_t) P.mmlt_dmax; smp.base_d = 4u * (uint32_t) P.mmlt_dmax;
+    smp.emitter_ident2 = false; smp.direct_ident = direct_ident; smp.x_dir = nullptr; smp.x_dir_n = 0u;
+    smp.reset_caches();
+    smp.select(SEG_SENSOR);
+}
+
+// Components the sensor, emitter and direct sampler consumed in one evaluation.
+struct SegDims { uint32_t s, e, d; };
+// Tierney & Mira's transition ratio Q1(y|z) / Q1(y|x) of a sampler triple: the product of the samplers' ratios
+// (drmlt_proc.cpp:633-637, drmlt_sampler.cpp:400-414), each over the dimensions either stage used, as ONE exponential of the
+// summed log densities. NSEG = 2 for mmlt (its direct sampler's first stage is the identity: ratio 1), 3 for bdpt. Leaves the
+// sampler on its last segment.
+// UNROLL: whether the loop over the segments is unrolled, a register-allocation matter of kernels that sit at their 256-register
+// cap. bdpt's is (each copy selects its segment with constants; rolled, k_mutate_bdpt<7, 2> spills a fifth vector register),
+// mmlt's is not (unrolled, k_mutate_mmlt<15> spills an eighth): DESIGN.md section 3.
+template <int NSEG, bool UNROLL> DEV float mira_ratio_segments(MSampler &smp, const SegDims n1, const SegDims n2) {
+    float num = 0.f, den = 0.f;
+#pragma unroll UNROLL ? NSEG : 1
+    for (int sg = 0; sg < NSEG; ++sg) {
+        const uint32_t nmax = sg == 0 ? max(n1.s, n2.s) : (sg == 1 ? max(n1.e, n2.e) : max(n1.d, n2.d));
+        const uint32_t dimStage = nmax > 0u ? nmax - 1u : 0u;
+        smp.select(sg);
+        // (not unrolled: the unrolled copies' compare masks were live at once and spilled scalar registers in every chain kernel)
+#pragma nounroll
+        for (uint32_t i = 0; i < dimStage; ++i) {
+            float yi = smp.y_raw(i);
+            num += kelemen_logpdf(smp.z_raw(i) - yi);
+            den += kelemen_logpdf(smp.x(i) - yi);
+        }
+    }
+    return __expf(num - den);
+}
+
 // ------------------------------------------------------------------ BSDF helpers (local frame)
 DEV DRoughConductor make_rc(const DBsdf &B) {
     return DRoughConductor{DMicrofacet{B.p[7] != 0.f, fmaxf(B.p[0], 1e-4f)}, mk3(B.p[1], B.p[2], B.p[3]), mk3(B.p[4], B.p[5], B.p[6]),

@@ -1,7 +1,9 @@
-// The decision logic of the chain loops, ONE copy for every chain kernel (k_mutate_v3 / v4, k_mutate_mmlt, k_mutate_bdpt):
-// acceptance rules of both stages, expectation weights, the event counters behind the seven ratios, and the
-// acceptance-map rule. The kernels differ in how a proposal is evaluated and where its splats live (a DSplat in
-// registers, a list in memory); what is decided from the luminances is the same code.
+// The decision logic of the chain loops, ONE copy for every chain kernel (k_mutate_v3 / v4 / v5, k_mutate_mmlt, k_mutate_bdpt):
+// the two-stage state machine (mh_digest: which rule applies at which stage, when Green goes on to the reverse move, when Mira's
+// ratio is needed, when a mutation is decided and who is adopted) over the acceptance rules of both stages, the expectation
+// weights, the event counters behind the seven ratios and the acceptance-map rule. The kernels differ in how a proposal is
+// evaluated and where its splats live (a DSplat in registers, a list in memory); what is decided from the luminances is the same
+// code, and the kernels call nothing of this file but mh_digest (k_mutate_pssmlt, another algorithm, counts with mh_count).
 //
 // Reference (paths relative to the checkout):
 //   stage 1 (Eq. 5), doSecond gating          src/integrators/drmlt/drmlt_proc.cpp:544-558
@@ -119,3 +121,60 @@ DEV int mh_amap_mark(bool mix, bool amap, bool large, bool acc1, bool acc2) {
     return acc1 ? (large ? AMAP_NONE : AMAP_RED) : AMAP_GREEN;
 }
 DEV f3 mh_amap_colour(int mark) { return mark == AMAP_RED ? mk3(1.f, 0.f, 0.f) : mk3(0.f, 1.f, 0.f); }
+
+// ------------------------------------------------------------------------------------------ the two-stage state machine
+// Rule switches of a render, wave-uniform: built by the caller from the parameter copy of the loop section it is in.
+struct MhRules {
+    bool mix, amap, timid_after_large;
+    int type; // 0 Green, 1 Mira, 2 orbital
+};
+// Outcome of one digested evaluation. !decided: `stage` has been advanced (1: second stage, 2: Green's reverse move) and the
+// chain evaluates again. decided: the mutation is over -- acc1 / acc2: the first- / second-stage proposal is adopted; w: the
+// expectation weights of the current state and the two proposals; amap: the acceptance-map mark (AMAP_*) for the state that is
+// being REPLACED (mh_amap_mark).
+struct MhDigest {
+    bool decided, acc1, acc2;
+    int amap;
+    MhWeights w;
+};
+
+// DRMLTRenderer::process / processMixture from the end of one evaluation to the next (drmlt_proc.cpp:518-770, 161-380).
+// `lum` is the luminance of the evaluation just finished: of y at stage 0, of z at stage 1, of the reverse move y* at stage 2;
+// y_lum / z_lum are those of the stages before it. `mira_ratio()` yields Q1(y|z) / Q1(y|x) and is called only when the rule
+// needs it: after a large step both proposals are uniform (ratio 1), and with min(1, y/z) >= 1 the rule rejects without it.
+// Counts the decided mutation (and every reverse evaluation) in `ct`; the mutation counter, the sampler state and the splats
+// belong to the caller.
+template <class MiraRatio>
+DEV MhDigest mh_digest(const MhRules R, bool large, float coin_acc1, float coin_acc2, float coin_mix, float lum, float cur_lum,
+                       float y_lum, float z_lum, float &a1, int &stage, Counters &ct, MiraRatio mira_ratio) {
+    MhDigest d{false, false, false, AMAP_NONE, {0.f, 0.f, 0.f}};
+    float a2 = 0.f;
+    if (stage == 0) {
+        bool do_second = false;
+        mh_first(R.mix, R.timid_after_large, large, lum, cur_lum, coin_acc1, coin_mix, a1, d.acc1, do_second);
+        if (do_second) { d.acc1 = false; stage = 1; return d; }
+    } else if (stage == 1) {
+        if (R.mix) {
+            a1 = 0.f; // the second proposal replaces the first
+            mh_second_mixture(lum, cur_lum, coin_acc2, a2, d.acc2);
+        } else if (!lum_invalid(lum)) {
+            if (R.type == 0) { stage = 2; return d; } // Green: evaluate the reverse move first
+            if (R.type == 1) {
+                float ratio = 1.f;
+                if (!large && !(fminf(1.f, y_lum / lum) >= 1.f)) ratio = mira_ratio();
+                mh_second_mira(y_lum, lum, cur_lum, a1, ratio, coin_acc2, a2, d.acc2);
+            } else {
+                mh_second_orbital(y_lum, lum, cur_lum, coin_acc2, a2, d.acc2);
+            }
+        }
+    } else {
+        ct.acc2b_rev += 1u << 16;
+        mh_second_green(lum, z_lum, cur_lum, a1, coin_acc2, a2, d.acc2);
+    }
+    const bool do_second = stage != 0;
+    d.decided = true;
+    d.w = mh_weights(R.mix, R.amap, do_second, a1, a2);
+    mh_count(ct, large, d.acc1, d.acc2, do_second);
+    d.amap = mh_amap_mark(R.mix, R.amap, large, d.acc1, d.acc2);
+    return d;
+}

@@ -90,7 +90,7 @@ DEV void load_params(DParams &dst, KArgPtr src) {
 // section uses are scalar loads at its head (scalar-cache hits) and dead at its end, instead of scalar registers that stay live --
 // and spill into vector lanes -- across the whole chain loop (k_mutate_v4: 200 -> 85 spilled SGPRs). The kernel's first parameter
 // must be the DParams block.
-#define SECTION_PARAMS_OF_KERNEL(name)                                                          \
+#define SECTION_PARAMS(name)                                                          \
     KArgPtr name##_q = (KArgPtr) __builtin_amdgcn_kernarg_segment_ptr();                        \
     asm volatile("" : "+s"(name##_q));                                                          \
     DParams name;                                                                               \

@@ -135,27 +135,18 @@ struct ChainState {
     float a1, coin_acc1, coin_acc2, coin_mix;
     uint32_t it, nd1, nd2;
     int stage;       // -1: no mutation in flight, 0/1/2: evaluating first / second / reverse
-    bool large, do_second;
+    bool large;
 };
 
 // The bookkeeping branch in four pieces so that k_mutate_v3 can share the two heavy ones
 // (committing D_eff dimensions, drawing the next mutation's uniforms) between a chain lane and
 // its helper lane:
-//   mh_decide  digest the finished evaluation; if the mutation is decided: weights + counters,
-//              returns the commit mode (0 none, SM_STAGE1 = adopt y, SM_STAGE2 = adopt z)
+//   mh_decide  digest the finished evaluation (device_mh.h: mh_digest); the caller splats a decided mutation --
+//              k_mutate_v3 at once, k_mutate_v4 / v5 through their LDS queue -- and commits the adopted proposal
 //   commit     x[k] = wrap(proposal[k]) for a range of dimensions           (shareable)
 //   mh_start   advance to the next evaluation (next stage or next mutation); returns which
 //              uniforms must be drawn (0 none, 1 first stage, 2 second stage)
 //   fill       Philox draws into LDS for a range of blocks                    (shareable)
-// Outcome of one digested evaluation. `decided`: the mutation is over and w = the expectation weights of the current
-// state, the first-stage and the second-stage proposal; `commit`: 0 none, SM_STAGE1 = adopt y, SM_STAGE2 = adopt z;
-// `amap`: acceptance-map mark (AMAP_*) for the pixel of the state that is being REPLACED (device_mh.h: mh_amap_mark).
-// The caller splats: k_mutate_v3 at once, k_mutate_v4 through its LDS queue.
-struct MhOutcome {
-    bool decided;
-    int commit, amap;
-    MhWeights w;
-};
 
 // Tierney & Mira's transition ratio Q1(y|z) / Q1(y|x) over the dimensions either stage used (drmlt_sampler.cpp:400-414)
 template <class SamplerT> DEV float mira_ratio(SamplerT &smp, uint32_t nd1, uint32_t nd2) {
@@ -171,55 +162,35 @@ template <class SamplerT> DEV float mira_ratio(SamplerT &smp, uint32_t nd1, uint
     return __expf(num - den);
 }
 
-template <class SamplerT> DEV MhOutcome mh_decide(const DParams &P, ChainState &cs, SamplerT &smp, PathState &ps, Counters &ct) {
-    const bool mix = P.use_mixture != 0;
-    MhOutcome out{false, 0, AMAP_NONE, {0.f, 0.f, 0.f}};
-    if (cs.stage < 0) return out; // nothing evaluated yet (first call of a launch)
-    float a2 = 0.f;
-    bool acc1 = false, acc2 = false;
+// commit mode of a decided mutation: 0 none, SM_STAGE1 = adopt y, SM_STAGE2 = adopt z
+DEV int mh_commit_mode(const MhDigest &d) { return d.acc1 ? SM_STAGE1 : (d.acc2 ? SM_STAGE2 : 0); }
+
+// What the path kernels add to mh_digest: the evaluation's result comes out of a PathState and is normalised, the dimensions each
+// stage consumed are kept for Mira's ratio, and a decided mutation advances the chain's counter (stage -1: between mutations).
+template <class SamplerT> DEV MhDigest mh_decide(const DParams &P, ChainState &cs, SamplerT &smp, PathState &ps, Counters &ct) {
+    if (cs.stage < 0) return MhDigest{false, false, false, AMAP_NONE, {0.f, 0.f, 0.f}}; // nothing evaluated yet (first call of a launch)
     DSplat res;
     res.px = ps.px; res.py = ps.py; res.r = ps.Li.x; res.g = ps.Li.y; res.b = ps.Li.z;
     res.lum = luminance3(ps.Li);
     normalize_splat(res, P);
     ct.rays += ps.nrays;
-    if (cs.stage == 0) {
-        cs.y = res; cs.nd1 = ps.k;
-        mh_first(mix, P.timid_after_large != 0, cs.large, res.lum, cs.cur.lum, cs.coin_acc1, cs.coin_mix, cs.a1, acc1, cs.do_second);
-        if (cs.do_second) { cs.stage = 1; return out; }
-    } else if (cs.stage == 1) {
-        cs.z = res; cs.nd2 = ps.k;
-        if (mix) {
-            cs.a1 = 0.f; // the second proposal replaces the first
-            mh_second_mixture(res.lum, cs.cur.lum, cs.coin_acc2, a2, acc2);
-        } else if (!lum_invalid(res.lum)) {
-            if (P.type == 0) { cs.stage = 2; return out; } // Green: evaluate the reverse move first
-            if (P.type == 1) {
-                float ratio = 1.f;
-                if (!cs.large && !(fminf(1.f, cs.y.lum / res.lum) >= 1.f)) ratio = mira_ratio(smp, cs.nd1, cs.nd2);
-                mh_second_mira(cs.y.lum, res.lum, cs.cur.lum, cs.a1, ratio, cs.coin_acc2, a2, acc2);
-            } else {
-                mh_second_orbital(cs.y.lum, res.lum, cs.cur.lum, cs.coin_acc2, a2, acc2);
-            }
-        }
-    } else {
-        ct.acc2b_rev += 1u << 16;
-        mh_second_green(res.lum, cs.z.lum, cs.cur.lum, cs.a1, cs.coin_acc2, a2, acc2);
-    }
-    out.decided = true;
-    out.w = mh_weights(mix, P.acceptance_map != 0, cs.do_second, cs.a1, a2);
-    mh_count(ct, cs.large, acc1, acc2, cs.do_second);
-    if (acc1 || acc2) out.commit = acc1 ? SM_STAGE1 : SM_STAGE2;
-    out.amap = mh_amap_mark(mix, P.acceptance_map != 0, cs.large, acc1, acc2);
-    cs.it++;
-    cs.stage = -1;
-    return out;
+    // (selected VALUES: `if (stage == 0) cs.y = res; else if (stage == 1) cs.z = res;` is merged into one store through a selected
+    // ADDRESS, and the chain state then lives in scratch memory -- see select_splat)
+    const bool first = cs.stage == 0, second = cs.stage == 1;
+    cs.y = select_splat(first, res, cs.y); cs.nd1 = first ? ps.k : cs.nd1;
+    cs.z = select_splat(second, res, cs.z); cs.nd2 = second ? ps.k : cs.nd2;
+    const MhRules R{P.use_mixture != 0, P.acceptance_map != 0, P.timid_after_large != 0, P.type};
+    const MhDigest d = mh_digest(R, cs.large, cs.coin_acc1, cs.coin_acc2, cs.coin_mix, res.lum, cs.cur.lum, cs.y.lum, cs.z.lum, cs.a1, cs.stage, ct,
+                                 [&]() { return mira_ratio(smp, cs.nd1, cs.nd2); });
+    if (d.decided) { cs.it++; cs.stage = -1; }
+    return d;
 }
 
 // k_mutate_v3: splat the decided mutation at once and adopt the accepted proposal. The three splats go through ONE
 // film_put site (the call expands to ~150 instructions; six inlined copies of it were a sixth of the kernel's code):
 // slot 0 current state, 1 first-stage, 2 second-stage proposal.
 DEV int mh_decide_splat(const DParams &P, ChainState &cs, LdsSampler &smp, PathState &ps, Counters &ct) {
-    const MhOutcome o = mh_decide(P, cs, smp, ps, ct);
+    const MhDigest o = mh_decide(P, cs, smp, ps, ct);
     if (!o.decided) return 0;
 #pragma nounroll
     for (int i = 0; i < 3; ++i) {
@@ -227,11 +198,12 @@ DEV int mh_decide_splat(const DParams &P, ChainState &cs, LdsSampler &smp, PathS
         const DSplat sp = select_splat(i == 0, cs.cur, select_splat(i == 1, cs.y, cs.z));
         if (w > 0.f) film_put(P, sp.px, sp.py, mk3(sp.r * w, sp.g * w, sp.b * w));
     }
-    if (o.commit) {
+    const int commit = mh_commit_mode(o);
+    if (commit) {
         if (o.amap) film_put(P, cs.cur.px, cs.cur.py, mh_amap_colour(o.amap)); // the state that is LEFT (device_mh.h)
-        cs.cur = select_splat(o.commit == SM_STAGE1, cs.y, cs.z);
+        cs.cur = select_splat(o.acc1, cs.y, cs.z);
     }
-    return o.commit;
+    return commit;
 }
 
 // DRMLTSampler::accept for dimensions [k0, k1): uCurrent = wrap(chosen proposal)
@@ -264,7 +236,6 @@ DEV int mh_start(const DParams &P, ChainState &cs, LdsSampler &smp, PathState &p
         smp.major = m;
         smp.large = cs.large;
         cs.stage = 0;
-        cs.do_second = false;
         cs.nd1 = cs.nd2 = 0u;
         fill = 1;
     } else if (cs.stage == 1) {
@@ -314,7 +285,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v3(DParams P, uint32_t n
     cs.cur.r = P.cur_r[cc]; cs.cur.g = P.cur_g[cc]; cs.cur.b = P.cur_b[cc];
     cs.y = cs.cur; cs.z = cs.cur;
     cs.a1 = 0.f; cs.coin_acc1 = cs.coin_acc2 = cs.coin_mix = 0.f;
-    cs.it = 0u; cs.nd1 = cs.nd2 = 0u; cs.stage = -1; cs.large = false; cs.do_second = false;
+    cs.it = 0u; cs.nd1 = cs.nd2 = 0u; cs.stage = -1; cs.large = false;
 
     LdsSampler smp;
     smp.key0 = P.key0; smp.key1 = P.key1; smp.chain = P.chain_offset + cc; smp.major = 0u;
@@ -432,6 +403,24 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v3(DParams P, uint32_t n
 }
 
 // ------------------------------------------------------------------------------------------
+// The run-ahead resolution of k_mutate_v4 / v5's bookkeeping branch. (Its decide step -- digesting mh_decide's outcome into the
+// cumulative weight and the three queued splats -- is written out in each kernel: as a shared function it cost the headline
+// build of k_mutate_v4 its scalar-register budget)
+// Between mutations (kind 4): go on while short of the target; beyond it (run-ahead, P.chain_done) while anybody in the grid is
+// short, up to `limit`. Called by the whole wave; `live`: the lane owns a chain (never a helper lane of k_mutate_v4). A wave all
+// of whose chains are at the target says so once (`reported`) in P.waves_left.
+DEV int mh_resolve_kind(const DParams &Pm, int kind, bool live, uint32_t done_now, uint32_t target, uint32_t limit, bool &reported, uint32_t lane) {
+    const bool under = __ballot(live && done_now < target) != 0ull;
+    bool more = under;
+    if (Pm.chain_done) {
+        if (!under && !reported) { reported = true; if (lane == 0) atomicSub(Pm.waves_left, 1u); }
+        if (!under) more = __builtin_amdgcn_readfirstlane((int) __hip_atomic_load(Pm.waves_left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0;
+    }
+    if (kind == 4) kind = (done_now < target || (done_now < limit && more)) ? 1 : 0;
+    return kind;
+}
+
+// ------------------------------------------------------------------------------------------
 // k_mutate_v4: k_mutate_v3's two lanes per chain, without its lock-step rounds.
 //
 // In v3 the bookkeeping branch fires when all 32 chains of a wave are parked: a round lasts as long as the longest of 32
@@ -534,14 +523,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
     // field it will ever need before the loop and then spills scalar registers into vector lanes all through the loop
     // (a sixth of the kernel's VALU instructions were v_readlane / v_writelane). Each loop section therefore works on its
     // own copy of the block, read through a kernarg pointer the compiler cannot see through: the fields a section uses
-    // are scalar loads at its head (scalar cache hits) and dead at its end.
-    typedef const DParams __attribute__((address_space(4))) *KArg;
-    const KArg kp = (KArg) __builtin_amdgcn_kernarg_segment_ptr();
-#define SECTION_PARAMS(name)                                               \
-    KArg name##_q = kp;                                                    \
-    asm volatile("" : "+s"(name##_q));                                     \
-    DParams name;                                                          \
-    load_params(name, name##_q)
+    // are scalar loads at its head (scalar cache hits) and dead at its end (SECTION_PARAMS, kernel_common.h).
     const uint32_t lane = threadIdx.x;
     const uint32_t sub = lane & 31u;
     const bool helper = lane >= 32u;
@@ -575,7 +557,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
         cs.cur.r = P.cur_r[cc]; cs.cur.g = P.cur_g[cc]; cs.cur.b = P.cur_b[cc];
         cs.y = cs.cur; cs.z = cs.cur;
         cs.a1 = 0.f; cs.coin_acc1 = cs.coin_acc2 = cs.coin_mix = 0.f;
-        cs.it = 0u; cs.nd1 = cs.nd2 = 0u; cs.stage = -1; cs.large = false; cs.do_second = false;
+        cs.it = 0u; cs.nd1 = cs.nd2 = 0u; cs.stage = -1; cs.large = false;
         path_init(P, ps);
         // Run-ahead (P.chain_done): `n_mut` is then the TARGET every chain must have reached when the launch ends, counted from
         // the chain's seeding; a chain that is there keeps mutating -- up to P.run_limit, the render's total -- for as long as
@@ -628,16 +610,16 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
             float e1x = 0.f, e1y = 0.f, e1r = 0.f, e1g = 0.f, e1b = 0.f;
             float e2x = 0.f, e2y = 0.f, e2r = 0.f, e2g = 0.f, e2b = 0.f;
             if (parked) {
-                const MhOutcome o = mh_decide(Pm, cs, smp, ps, ct);
+                const MhDigest o = mh_decide(Pm, cs, smp, ps, ct);
                 if (o.decided) {
                     cum += o.w.w0;
-                    const bool a1st = o.commit == SM_STAGE1, a2nd = o.commit == SM_STAGE2;
+                    const bool a1st = o.acc1, a2nd = o.acc2;
                     // rejected proposals are splatted now, an adopted one carries its weight into `cum`
                     want1 = !a1st && o.w.w1 > 0.f;
                     e1x = cs.y.px; e1y = cs.y.py; e1r = cs.y.r * o.w.w1; e1g = cs.y.g * o.w.w1; e1b = cs.y.b * o.w.w1;
                     want2 = !a2nd && o.w.w2 > 0.f;
                     e2x = cs.z.px; e2y = cs.z.py; e2r = cs.z.r * o.w.w2; e2g = cs.z.g * o.w.w2; e2b = cs.z.b * o.w.w2;
-                    if (o.commit) {
+                    if (o.acc1 || o.acc2) {
                         want0 = cum > 0.f;
                         e0x = cs.cur.px; e0y = cs.cur.py; e0r = cs.cur.r * cum; e0g = cs.cur.g * cum; e0b = cs.cur.b * cum;
                         cum = a1st ? o.w.w1 : o.w.w2;
@@ -647,21 +629,11 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                             want1 = true; e1x = e0x; e1y = e0y; e1r = mc.x; e1g = mc.y; e1b = mc.z;
                         }
                     }
-                    commit = o.commit;
+                    commit = mh_commit_mode(o);
                 }
                 kind = cs.stage < 0 ? 4 : (cs.stage == 1 ? 2 : 3); // 4: between mutations -- resolved below
             }
-            {
-                // between mutations: go on while short of the target; beyond it (run-ahead) while anybody in the grid is short
-                const uint32_t done_now = base + cs.it;
-                const bool under = __ballot(!helper && live && done_now < target) != 0ull;
-                bool more = under;
-                if (Pm.chain_done) {
-                    if (!under && !reported) { reported = true; if (lane == 0) atomicSub(Pm.waves_left, 1u); }
-                    if (!under) more = __builtin_amdgcn_readfirstlane((int) __hip_atomic_load(Pm.waves_left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0;
-                }
-                if (kind == 4) kind = (done_now < target || (done_now < limit && more)) ? 1 : 0;
-            }
+            kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
             v4_enqueue(L, qn, want0, e0x, e0y, e0r, e0g, e0b);
             v4_enqueue(L, qn, want1, e1x, e1y, e1r, e1g, e1b);
             v4_enqueue(L, qn, want2, e2x, e2y, e2r, e2g, e2b);
@@ -701,7 +673,6 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                 cs.large = cn[0] < Pm.p_large;
                 cs.coin_acc1 = cn[S]; cs.coin_acc2 = cn[2u * S]; cs.coin_mix = cn[3u * S];
                 cs.stage = 0;
-                cs.do_second = false;
                 cs.nd1 = cs.nd2 = 0u;
             }
             const unsigned long long m3 = STAMP();
@@ -865,7 +836,6 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
     // the epilogue reads its own copy of the block too: otherwise the compiler keeps the pointers it shares with the prologue
     // (state rows, film, counters) in scalar registers -- spilled -- all through the loop
     SECTION_PARAMS(Pe);
-#undef SECTION_PARAMS
     // "Perform the last splat": the current states with what they have accumulated since they were adopted
     const V4Layout Y = v4_layout(Pe, QCAP);
     v4_enqueue(Y.L, qn, live && cum > 0.f, cs.cur.px, cs.cur.py, cs.cur.r * cum, cs.cur.g * cum, cs.cur.b * cum);
@@ -1127,13 +1097,6 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, ROWS_MEM ? V5_ROWS_MEM_WAVES : 2)
     constexpr bool COIN_ROWS = FLAT || STACK16; // coins drawn one mutation ahead by the flattened proposal pass (else: per lane, when a mutation starts)
     // per-section copies of the parameter block, read through a kernarg pointer the compiler cannot see through (see k_mutate_v4):
     // the fields a section uses are scalar loads at its head and dead at its end, instead of ~200 spilled scalar registers
-    typedef const DParams __attribute__((address_space(4))) *KArg;
-    const KArg kp = (KArg) __builtin_amdgcn_kernarg_segment_ptr();
-#define SECTION_PARAMS(name)                                               \
-    KArg name##_q = kp;                                                    \
-    asm volatile("" : "+s"(name##_q));                                     \
-    DParams name;                                                          \
-    load_params(name, name##_q)
     SECTION_PARAMS(P0);
     const uint32_t lane = threadIdx.x;
     const uint32_t wave_base = blockIdx.x * 64u;
@@ -1166,7 +1129,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, ROWS_MEM ? V5_ROWS_MEM_WAVES : 2)
     cs.cur.r = P0.cur_r[cc]; cs.cur.g = P0.cur_g[cc]; cs.cur.b = P0.cur_b[cc];
     cs.y = cs.cur; cs.z = cs.cur;
     cs.a1 = 0.f; cs.coin_acc1 = cs.coin_acc2 = cs.coin_mix = 0.f;
-    cs.it = 0u; cs.nd1 = cs.nd2 = 0u; cs.stage = -1; cs.large = false; cs.do_second = false;
+    cs.it = 0u; cs.nd1 = cs.nd2 = 0u; cs.stage = -1; cs.large = false;
     float cum = 0.f; // weight of the current state since it was adopted (one splat per residence, as k_mutate_v4)
     uint32_t qn = 0u;
     Counters ct = {0u, 0u, 0u, 0u, 0u};
@@ -1284,15 +1247,15 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, ROWS_MEM ? V5_ROWS_MEM_WAVES : 2)
                         smp.mira_x = Pm.x + cc; smp.mira_stride = Pm.n_chains; smp.mira_k0 = Pm.key0; smp.mira_k1 = Pm.key1;
                         smp.mira_major = base + cs.it; smp.mira_chain = Pm.chain_offset + cc; smp.reset_caches();
                     }
-                    const MhOutcome o = mh_decide(Pm, cs, smp, ps, ct);
+                    const MhDigest o = mh_decide(Pm, cs, smp, ps, ct);
                     if (o.decided) {
                         cum += o.w.w0;
-                        const bool a1st = o.commit == SM_STAGE1, a2nd = o.commit == SM_STAGE2;
+                        const bool a1st = o.acc1, a2nd = o.acc2;
                         want1 = !a1st && o.w.w1 > 0.f;
                         e1x = cs.y.px; e1y = cs.y.py; e1r = cs.y.r * o.w.w1; e1g = cs.y.g * o.w.w1; e1b = cs.y.b * o.w.w1;
                         want2 = !a2nd && o.w.w2 > 0.f;
                         e2x = cs.z.px; e2y = cs.z.py; e2r = cs.z.r * o.w.w2; e2g = cs.z.g * o.w.w2; e2b = cs.z.b * o.w.w2;
-                        if (o.commit) {
+                        if (o.acc1 || o.acc2) {
                             want0 = cum > 0.f;
                             e0x = cs.cur.px; e0y = cs.cur.py; e0r = cs.cur.r * cum; e0g = cs.cur.g * cum; e0b = cs.cur.b * cum;
                             cum = a1st ? o.w.w1 : o.w.w2;
@@ -1302,21 +1265,11 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, ROWS_MEM ? V5_ROWS_MEM_WAVES : 2)
                                 want1 = true; e1x = e0x; e1y = e0y; e1r = mc.x; e1g = mc.y; e1b = mc.z;
                             }
                         }
-                        commit = o.commit;
+                        commit = mh_commit_mode(o);
                     }
                     kind = cs.stage < 0 ? 4 : (cs.stage == 1 ? 2 : 3); // 3: Green's reverse move
                 }
-                {
-                    // between mutations: go on while short of the target; beyond it (run-ahead) while anybody in the grid is short
-                    const uint32_t done_now = base + cs.it;
-                    const bool under = __ballot(live && done_now < target) != 0ull;
-                    bool more = under;
-                    if (Pm.chain_done) {
-                        if (!under && !reported) { reported = true; if (lane == 0) atomicSub(Pm.waves_left, 1u); }
-                        if (!under) more = __builtin_amdgcn_readfirstlane((int) __hip_atomic_load(Pm.waves_left, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0;
-                    }
-                    if (kind == 4) kind = (done_now < target || (done_now < limit && more)) ? 1 : 0;
-                }
+                kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
                 if constexpr (QCAP != 0u) { // the queue holds QCAP entries, a round adds at most 64
                     v4_enqueue(Lq, qn, want0, e0x, e0y, e0r, e0g, e0b);
                     if (qn + 64u > QCAP) v4_flush(Pm, Lq, qn, lane);
@@ -1391,7 +1344,6 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, ROWS_MEM ? V5_ROWS_MEM_WAVES : 2)
                         cs.coin_acc1 = u32_to_unit(coins.y); cs.coin_acc2 = u32_to_unit(coins.z); cs.coin_mix = u32_to_unit(coins.w);
                     }
                     cs.stage = 0;
-                    cs.do_second = false;
                     cs.nd1 = cs.nd2 = 0u;
                 }
                 // ---- proposals, flattened: items (chain j, Philox block b) -> dimensions 4b .. 4b+3 of y from the state in device
@@ -1571,7 +1523,6 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, ROWS_MEM ? V5_ROWS_MEM_WAVES : 2)
     }
 #undef STAMP5
     SECTION_PARAMS(Pe);
-#undef SECTION_PARAMS
     if (STAMPS && lane == 0) {
         atomicAdd(Pe.stats + 16, t_mh); atomicAdd(Pe.stats + 17, t_trace); atomicAdd(Pe.stats + 18, t_step); atomicAdd(Pe.stats + 19, n_outer);
         atomicAdd(Pe.stats + 23, n_mh); atomicAdd(Pe.stats + 24, n_parked); atomicAdd(Pe.stats + 25, n_stepping);

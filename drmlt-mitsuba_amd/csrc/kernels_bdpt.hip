@@ -15,17 +15,6 @@
 DEV uint32_t bdpt_nx(const DParams &P) { return (uint32_t) (P.mmlt_S + P.mmlt_E + P.bd_Dd); } // components of a chain's state
 DEV uint32_t bdpt_nx_lds(const DParams &P) { return (uint32_t) (P.mmlt_S + P.mmlt_E); }        // ... of which LDS holds the two walks'
 
-DEV void bsampler_setup(MSampler &smp, const DParams &P, uint32_t lane) {
-    smp.key0 = P.key0; smp.key1 = P.key1;
-    smp.type = P.type; smp.sigma2 = P.sigma2; smp.large = false;
-    smp.lane = lane; smp.arr = nullptr;
-    smp.S = (uint32_t) P.mmlt_S; smp.E = (uint32_t) P.mmlt_E;
-    smp.base_e = 2u * (uint32_t) P.mmlt_dmax; smp.base_d = 4u * (uint32_t) P.mmlt_dmax;
-    smp.emitter_ident2 = false; smp.direct_ident = false; smp.x_dir = nullptr; smp.x_dir_n = 0u;
-    smp.reset_caches();
-    smp.select(SEG_SENSOR);
-}
-
 DEV float *list_col(const DParams &P, int slot, uint32_t chain) {
     return P.bd_lists + (size_t) slot * (size_t) bdpt_list_rows(P.max_depth) * P.n_chains_alloc + chain;
 }
@@ -87,7 +76,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_bootstrap_bdpt(DParams P, uint3
     const bool has_col = c < P.n_chains_alloc;
     const uint32_t cc = has_col ? c : P.n_chains_alloc - 1u;
     MSampler smp;
-    bsampler_setup(smp, P, lane);
+    msampler_setup(smp, P, lane, false);
     smp.chain = P.boot_stream; smp.mode = SM_BOOT;
     const GlobalTables T{P.shade, P.bsdfs, P.emitters};
     for (uint32_t i0 = blockIdx.x * CHAIN_BLOCK; i0 < n; i0 += P.n_chains_alloc) { // the whole wave makes every call (eval_bdpt)
@@ -109,7 +98,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_init_chains_bdpt(DParams P, con
     const bool live = c0 < P.n_chains;
     const uint32_t c = live ? c0 : P.n_chains - 1u;
     MSampler smp;
-    bsampler_setup(smp, P, lane);
+    msampler_setup(smp, P, lane, false);
     smp.chain = P.boot_stream; smp.major = seed_index[c]; smp.mode = SM_BOOT;
     const GlobalTables T{P.shade, P.bsdfs, P.emitters};
     BdptResult R;
@@ -159,14 +148,13 @@ template <int FEAT, int OCC, bool LDS_BSDFS = false> __global__ void __launch_bo
     float cum = 0.f; // weight the current state has gathered since it was adopted
 
     MSampler smp;
-    bsampler_setup(smp, P, lane);
+    msampler_setup(smp, P, lane, false);
     smp.chain = P.chain_offset + cc;
     float *const xdir = P.x + (size_t) NX * P.n_chains + cc; // the direct sampler's components of this chain
     smp.x_dir = xdir; smp.x_dir_n = P.n_chains;
     const GlobalTables T{P.shade, P.bsdfs, P.emitters};
     Counters ct = {0u, 0u, 0u, 0u, 0u};
-    const bool amap = P.acceptance_map != 0;
-    const bool mix = P.use_mixture != 0;
+    const MhRules rules{P.use_mixture != 0, P.acceptance_map != 0, P.timid_after_large != 0, P.type};
 
     const bool dbg = (P.debug & 128) != 0;
     unsigned long long t_stages = 0, t_splat = 0, t_commit = 0;
@@ -179,7 +167,7 @@ template <int FEAT, int OCC, bool LDS_BSDFS = false> __global__ void __launch_bo
     uint32_t it = 0u, work = 0u; // work: path evaluations of this launch
     int stage = 0;
     float y_lum = 0.f, z_lum = 0.f, a1 = 0.f;
-    uint32_t ns1 = 0, ne1 = 0, nd1 = 0, ns2 = 0, ne2 = 0, nd2 = 0;
+    SegDims n1 = {0u, 0u, 0u}, n2 = {0u, 0u, 0u}; // components each stage consumed
     for (;;) {
         const bool run = live && it < n_mut;
         if (!__builtin_amdgcn_ballot_w64(run)) break;
@@ -189,8 +177,6 @@ template <int FEAT, int OCC, bool LDS_BSDFS = false> __global__ void __launch_bo
         smp.major = m;
         smp.large = large;
         const unsigned long long b0 = BSTAMP();
-        float a2 = 0.f;
-        bool acc1 = false, acc2 = false, decided = true;
         smp.mode = stage == 0 ? SM_STAGE1 : (stage == 1 ? SM_STAGE2 : SM_REVERSE);
         BdptResult R;
         // Green's reverse path only needs its luminance; it is written over the first-stage list, which is rejected
@@ -200,67 +186,37 @@ template <int FEAT, int OCC, bool LDS_BSDFS = false> __global__ void __launch_bo
         else eval_bdpt<FEAT>(P, T, smp, run, cc, NX, target, R);
         if (!run) continue;
         ++work;
-        {
-            ct.rays += R.nrays;
-            const float lum = list_finalize(P, target, R.lum);
-            if (stage == 0) {
-                bool doSecond = false;
-                y_lum = lum; ns1 = R.n_sensor; ne1 = R.n_emitter; nd1 = R.n_direct;
-                z_lum = 0.f; ns2 = ne2 = nd2 = 0u;
-                mh_first(mix, P.timid_after_large != 0, large, y_lum, cur_lum, u32_to_unit(coins.y), u32_to_unit(coins.w), a1, acc1, doSecond);
-                if (doSecond) { stage = 1; decided = false; }
-            } else if (stage == 1) {
-                z_lum = lum; ns2 = R.n_sensor; ne2 = R.n_emitter; nd2 = R.n_direct;
-                if (mix) { // the second proposal replaces the first
-                    a1 = 0.f;
-                    mh_second_mixture(z_lum, cur_lum, u32_to_unit(coins.z), a2, acc2);
-                } else if (lum_invalid(z_lum)) {
-                } else if (P.type == 0) {
-                    // Green: the first-stage splats must reach the film before the reverse move reuses their list
-                    if (!amap && a1 > 0.f) list_splat(P, L1, y_lum, a1);
-                    stage = 2; decided = false;
-                } else if (P.type == 1) {
-                    float ratio = 1.f;
-                    if (!large && !(fminf(1.f, y_lum / z_lum) >= 1.f)) { // (a large step -- here only with timidAfterLarge -- has no kernel ratio: uniform proposals both times)
-                        float num = 0.f, den = 0.f;
-                        for (int sg = 0; sg < 3; ++sg) {
-                            const uint32_t nmax = sg == 0 ? max(ns1, ns2) : (sg == 1 ? max(ne1, ne2) : max(nd1, nd2));
-                            const uint32_t dimStage = nmax > 0u ? nmax - 1u : 0u;
-                            smp.select(sg);
-                            for (uint32_t i = 0; i < dimStage; ++i) {
-                                float yi = smp.y_raw(i);
-                                num += kelemen_logpdf(smp.z_raw(i) - yi);
-                                den += kelemen_logpdf(smp.x(i) - yi);
-                            }
-                        }
-                        ratio = __expf(num - den);
-                    }
-                    mh_second_mira(y_lum, z_lum, cur_lum, a1, ratio, u32_to_unit(coins.z), a2, acc2);
-                } else {
-                    mh_second_orbital(y_lum, z_lum, cur_lum, u32_to_unit(coins.z), a2, acc2);
-                }
-            } else {
-                ct.acc2b_rev += 1u << 16;
-                mh_second_green(lum, z_lum, cur_lum, a1, u32_to_unit(coins.z), a2, acc2);
-            }
+        ct.rays += R.nrays;
+        const float lum = list_finalize(P, target, R.lum);
+        if (stage == 0) {
+            y_lum = lum; n1 = SegDims{R.n_sensor, R.n_emitter, R.n_direct};
+            z_lum = 0.f; n2 = SegDims{0u, 0u, 0u};
+        } else if (stage == 1) {
+            z_lum = lum; n2 = SegDims{R.n_sensor, R.n_emitter, R.n_direct};
         }
+        const MhDigest d = mh_digest(rules, large, u32_to_unit(coins.y), u32_to_unit(coins.z), u32_to_unit(coins.w), lum, cur_lum, y_lum, z_lum, a1, stage, ct,
+                                     [&]() { return mira_ratio_segments<3, true>(smp, n1, n2); });
         const unsigned long long b1 = BSTAMP();
-        if (!decided) { t_stages += b1 - b0; continue; }
-        const bool doSecond = stage != 0;
-        const bool y_splatted = stage == 2 && !amap; // Green went on to the reverse move
+        if (!d.decided) {
+            // Green goes on to the reverse move: the first-stage splats must reach the film before it reuses their list
+            if (stage == 2 && !rules.amap && a1 > 0.f) list_splat(P, L1, y_lum, a1);
+            t_stages += b1 - b0;
+            continue;
+        }
+        const bool acc1 = d.acc1, acc2 = d.acc2;
+        const bool y_splatted = stage == 2 && !rules.amap; // Green went on to the reverse move
 
         // Expectation weights (device_mh.h). The current state's share is accumulated and its list splatted once, when the
         // state is replaced or the launch ends (the reference's pssmlt loop does the same, pssmlt_proc.cpp:205-228): the
         // same film, one list splat per mutation instead of two or three. An adopted proposal carries its weight into
         // `cum`. In an acceptance-map run of the delayed-rejection loop all three weights are zero.
-        const MhWeights w = mh_weights(mix, amap, doSecond, a1, a2);
+        const MhWeights w = d.w;
         cum += w.w0;
         if (acc1 || acc2) { list_splat(P, L0, cur_lum, cum); cum = acc1 ? w.w1 : w.w2; }
         if (!acc1 && !y_splatted) list_splat(P, L1, y_lum, w.w1);
         if (!acc2) list_splat(P, L2, z_lum, w.w2);
 
         const unsigned long long b2 = BSTAMP();
-        mh_count(ct, large, acc1, acc2, doSecond);
 
         if (acc1 || acc2) {
             for (int sg = 0; sg < 3; ++sg) { // every component of the three samplers (DRMLTSampler::accept, drmlt_sampler.cpp:189-199)
@@ -277,8 +233,7 @@ template <int FEAT, int OCC, bool LDS_BSDFS = false> __global__ void __launch_bo
             cur_lum = acc1 ? y_lum : z_lum;
             // acceptance map: every splat position of the list that WAS current -- after the swap that is the proposal's
             // slot, exactly as in the reference (drmlt_proc.cpp:693-709; device_mh.h)
-            const int mark = mh_amap_mark(mix, amap, large, acc1, acc2);
-            if (mark) list_splat_const(P, acc1 ? L1 : L2, mh_amap_colour(mark));
+            if (d.amap) list_splat_const(P, acc1 ? L1 : L2, mh_amap_colour(d.amap));
         }
         ++it;
         stage = 0;
@@ -306,7 +261,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_eval_lists_bdpt(DParams P, cons
     const bool has_col = c0 < P.n_chains_alloc;
     const uint32_t c = has_col ? c0 : P.n_chains_alloc - 1u;
     MSampler smp;
-    bsampler_setup(smp, P, lane);
+    msampler_setup(smp, P, lane, false);
     smp.chain = 0u; smp.major = 0u; smp.mode = SM_ARRAY;
     const GlobalTables T{P.shade, P.bsdfs, P.emitters};
     const size_t na = P.n_chains_alloc;

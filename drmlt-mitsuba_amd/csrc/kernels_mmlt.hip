@@ -12,23 +12,12 @@
 
 DEV uint32_t mmlt_nx(const DParams &P) { return (uint32_t) (P.mmlt_S + P.mmlt_E + 1); }
 
-DEV void msampler_setup(MSampler &smp, const DParams &P, uint32_t lane) {
-    smp.key0 = P.key0; smp.key1 = P.key1;
-    smp.type = P.type; smp.sigma2 = P.sigma2; smp.large = false;
-    smp.lane = lane; smp.arr = nullptr;
-    smp.S = (uint32_t) P.mmlt_S; smp.E = (uint32_t) P.mmlt_E;
-    smp.base_e = 2u * (uint32_t) P.mmlt_dmax; smp.base_d = 4u * (uint32_t) P.mmlt_dmax;
-    smp.emitter_ident2 = false; smp.direct_ident = true; smp.x_dir = nullptr; smp.x_dir_n = 0u;
-    smp.reset_caches();
-    smp.select(SEG_SENSOR);
-}
-
 __global__ void __launch_bounds__(CHAIN_BLOCK) k_bootstrap_mmlt(DParams P, uint32_t n, float *lum_out) {
     const uint32_t lane = threadIdx.x;
     const uint32_t i = blockIdx.x * CHAIN_BLOCK + lane;
     if (i >= n) return;
     MSampler smp;
-    msampler_setup(smp, P, lane);
+    msampler_setup(smp, P, lane, true);
     smp.chain = P.boot_stream; smp.major = i; smp.mode = SM_BOOT;
     const GlobalTables T{P.shade, P.bsdfs, P.emitters};
     MmltResult R;
@@ -44,7 +33,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_init_chains_mmlt(DParams P, con
     const uint32_t idx = seed_index[c];
     const int depth = (int) (idx % (uint32_t) P.max_depth) + 1;
     MSampler smp;
-    msampler_setup(smp, P, lane);
+    msampler_setup(smp, P, lane, true);
     smp.chain = P.boot_stream; smp.major = idx; smp.mode = SM_BOOT;
     const GlobalTables T{P.shade, P.bsdfs, P.emitters};
     MmltResult R;
@@ -99,12 +88,11 @@ template <int FEAT, bool LDS_TABLES = false> __global__ void __launch_bounds__(C
     const uint32_t usedS = 2u * (uint32_t) (depth + 1), usedE = 2u * (uint32_t) depth; // components a depth-`depth` path can consume
 
     MSampler smp;
-    msampler_setup(smp, P, lane);
+    msampler_setup(smp, P, lane, true);
     smp.chain = P.chain_offset + cc;
     const GlobalTables T{P.shade, P.bsdfs, P.emitters};
     Counters ct = {0u, 0u, 0u, 0u, 0u};
-    const bool amap = P.acceptance_map != 0;
-    const bool mix = P.use_mixture != 0;
+    const MhRules rules{P.use_mixture != 0, P.acceptance_map != 0, P.timid_after_large != 0, P.type}; // (drmlt_create refuses timidAfterLarge for mmlt)
 
     // Chains run free: every pass of the loop evaluates ONE path per lane -- the first stage of the lane's next mutation, or the
     // second stage / Green's reverse move of the one it is in. (In a lockstep loop over mutations with the stages inside, the few
@@ -115,7 +103,7 @@ template <int FEAT, bool LDS_TABLES = false> __global__ void __launch_bounds__(C
     y.lum = 0.f; y.px = y.py = y.r = y.g = y.b = 0.f;
     z = y;
     int y_t = 0, z_t = 0;
-    uint32_t ns1 = 0, ne1 = 0, ns2 = 0, ne2 = 0;
+    SegDims n1 = {0u, 0u, 0u}, n2 = {0u, 0u, 0u}; // components each stage consumed (the direct sampler's do not enter Mira's ratio)
     float a1 = 0.f;
     for (;;) {
         const bool run = live && it < n_mut;
@@ -128,64 +116,29 @@ template <int FEAT, bool LDS_TABLES = false> __global__ void __launch_bounds__(C
         smp.large = large;
         // fixEmitterPath: the emitter sampler moves in the second stage only for pure light tracing (drmlt_proc.cpp:566-573)
         smp.emitter_ident2 = P.fix_emitter_path != 0 && cur_t != 1;
-        float a2 = 0.f;
-        bool acc1 = false, acc2 = false, decided = true;
-        {
-            smp.mode = stage == 0 ? SM_STAGE1 : (stage == 1 ? SM_STAGE2 : SM_REVERSE);
-            MmltResult R;
-            if (LDS_TABLES) eval_mmlt<FEAT>(P, LT, smp, depth, NX, R);
-            else eval_mmlt<FEAT>(P, T, smp, depth, NX, R);
-            ++work;
-            ct.rays += R.nrays;
-            DSplat res = R.splat;
-            normalize_splat(res, P);
-            if (stage == 0) {
-                bool doSecond = false;
-                y = res; y_t = R.t; ns1 = R.n_sensor; ne1 = R.n_emitter;
-                z.lum = 0.f; z.px = z.py = z.r = z.g = z.b = 0.f; z_t = 0; ns2 = ne2 = 0u;
-                mh_first(mix, false, large, y.lum, cur.lum, u32_to_unit(coins.y), u32_to_unit(coins.w), a1, acc1, doSecond); // timidAfterLarge is refused for mmlt
-                if (doSecond) { stage = 1; decided = false; }
-            } else if (stage == 1) {
-                z = res; z_t = R.t; ns2 = R.n_sensor; ne2 = R.n_emitter;
-                if (mix) { // the second proposal replaces the first
-                    a1 = 0.f;
-                    mh_second_mixture(z.lum, cur.lum, u32_to_unit(coins.z), a2, acc2);
-                } else if (lum_invalid(z.lum)) {
-                } else if (P.type == 0) { // Green: the reverse move first
-                    stage = 2; decided = false;
-                } else if (P.type == 1) { // Tierney & Mira: product of the three samplers' ratios (drmlt_proc.cpp:633-637)
-                    float ratio = 1.f;
-                    if (!(fminf(1.f, y.lum / z.lum) >= 1.f)) { // (a large step never gets here: no second stage after it)
-                        float num = 0.f, den = 0.f;
-                        for (int sg = 0; sg < 2; ++sg) { // the direct sampler's first stage is the identity: ratio 1
-                            const uint32_t nmax = sg == 0 ? max(ns1, ns2) : max(ne1, ne2);
-                            const uint32_t dimStage = nmax > 0u ? nmax - 1u : 0u;
-                            smp.select(sg);
-                            for (uint32_t i = 0; i < dimStage; ++i) {
-                                float yi = smp.y_raw(i);
-                                num += kelemen_logpdf(smp.z_raw(i) - yi);
-                                den += kelemen_logpdf(smp.x(i) - yi);
-                            }
-                        }
-                        ratio = __expf(num - den);
-                    }
-                    mh_second_mira(y.lum, z.lum, cur.lum, a1, ratio, u32_to_unit(coins.z), a2, acc2);
-                } else {
-                    mh_second_orbital(y.lum, z.lum, cur.lum, u32_to_unit(coins.z), a2, acc2);
-                }
-            } else {
-                ct.acc2b_rev += 1u << 16;
-                mh_second_green(res.lum, z.lum, cur.lum, a1, u32_to_unit(coins.z), a2, acc2);
-            }
+        smp.mode = stage == 0 ? SM_STAGE1 : (stage == 1 ? SM_STAGE2 : SM_REVERSE);
+        MmltResult R;
+        if (LDS_TABLES) eval_mmlt<FEAT>(P, LT, smp, depth, NX, R);
+        else eval_mmlt<FEAT>(P, T, smp, depth, NX, R);
+        ++work;
+        ct.rays += R.nrays;
+        DSplat res = R.splat;
+        normalize_splat(res, P);
+        if (stage == 0) {
+            y = res; y_t = R.t; n1 = SegDims{R.n_sensor, R.n_emitter, 0u};
+            z.lum = 0.f; z.px = z.py = z.r = z.g = z.b = 0.f; z_t = 0; n2 = SegDims{0u, 0u, 0u};
+        } else if (stage == 1) {
+            z = res; z_t = R.t; n2 = SegDims{R.n_sensor, R.n_emitter, 0u};
         }
-        if (!decided) continue;
-        const bool doSecond = stage != 0;
+        const MhDigest d = mh_digest(rules, large, u32_to_unit(coins.y), u32_to_unit(coins.z), u32_to_unit(coins.w), res.lum, cur.lum, y.lum, z.lum, a1, stage, ct,
+                                     [&]() { return mira_ratio_segments<2, false>(smp, n1, n2); });
+        if (!d.decided) continue;
+        const bool acc1 = d.acc1, acc2 = d.acc2;
 
-        const MhWeights w = mh_weights(mix, amap, doSecond, a1, a2);
+        const MhWeights w = d.w;
         if (w.w0 > 0.f) film_put(P, cur.px, cur.py, mk3(cur.r * w.w0, cur.g * w.w0, cur.b * w.w0));
         if (w.w1 > 0.f) film_put(P, y.px, y.py, mk3(y.r * w.w1, y.g * w.w1, y.b * w.w1));
         if (w.w2 > 0.f) film_put(P, z.px, z.py, mk3(z.r * w.w2, z.g * w.w2, z.b * w.w2));
-        mh_count(ct, large, acc1, acc2, doSecond);
 
         if (acc1 || acc2) {
             // DRMLTSampler::accept on the three samplers: every component a path of this depth can consume
@@ -198,8 +151,7 @@ template <int FEAT, bool LDS_TABLES = false> __global__ void __launch_bounds__(C
                     if (smp.type == 2 && (k & 1u)) smp.pair_base = 0xffffffffu; // the pair cache holds the old x
                 }
             }
-            const int mark = mh_amap_mark(mix, amap, large, acc1, acc2);
-            if (mark) film_put(P, cur.px, cur.py, mh_amap_colour(mark)); // at the state that is LEFT (device_mh.h)
+            if (d.amap) film_put(P, cur.px, cur.py, mh_amap_colour(d.amap)); // at the state that is LEFT (device_mh.h)
             cur = select_splat(acc1, y, z);
             cur_t = acc1 ? y_t : z_t;
         }
@@ -223,7 +175,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_eval_paths_mmlt(DParams P, cons
     const uint32_t i = blockIdx.x * CHAIN_BLOCK + lane;
     if (i >= n) return;
     MSampler smp;
-    msampler_setup(smp, P, lane);
+    msampler_setup(smp, P, lane, true);
     smp.chain = 0u; smp.major = 0u; smp.mode = SM_ARRAY;
     smp.arr = u + (size_t) i * dim;
     const int depth = (int) smp.arr[P.mmlt_S + P.mmlt_E + 1];
