@@ -32,6 +32,12 @@ enum { SM_BOOT = 0, SM_ARRAY = 1, SM_STAGE1 = 2, SM_STAGE2 = 3, SM_REVERSE = 4, 
 // drmlt_sampler.h:140-144: y > 1 ? 2 - y : (y <= 0 ? |y| : y). For 0 < y <= 1, |y| = y, so two selects collapse into
 // one select on an |.|-modified operand (the nested form compiled to two exec-mask branches per component).
 DEV float wrap01(float y) { return y > 1.f ? 2.f - y : fabsf(y); }
+// A value that wrap01 maps back onto v, bit for bit, for every v that wrap01 returns: v itself inside [0, 1] (and for a NaN),
+// where wrap01 is the identity; outside -- perturbations of more than one, which no sane setting produces -- v > 1 came from -v,
+// and v < 0 from 2 - v (an exact difference: y >= 2 is a multiple of 2^-22, and so is 2 - y). Checked over all 2^32 arguments
+// of wrap01: one exception, y = 2^25 + 4, where 2 - y is a rounding tie. k_mutate_v4 keeps its current state unwrapped and
+// wraps it where it is read; it loads a stored (wrapped) state through this.
+DEV float unwrap01(float v) { return v < 0.f ? 2.f - v : (v > 1.f ? -v : v); }
 
 #define KELEMEN_S1 (1.0f / 1024.0f)
 #define KELEMEN_S2 (1.0f / 64.0f)
@@ -298,22 +304,27 @@ struct LdsSampler {
 // The proposals themselves are parked in LDS, not the uniforms they are made of: the bookkeeping branch of k_mutate_v4
 // evaluates the transition kernels for ALL dimensions of the chains that start an evaluation, flattened over the 64
 // lanes of the wave (items = chain x Philox block, every lane busy), so that inside the divergent path step a PSS
-// component is one LDS read and a reflection. Rows (stride `stride` floats, column = chain):
-//   x  [0 .. D)    current state
-//   y  [D4 rows]   first-stage proposal, unwrapped (a large step: the uniforms themselves)
-//   z  [D4 rows]   second-stage proposal, unwrapped
+// component is one LDS read and a reflection. Three row groups of D4 rows each (stride `stride` floats, column = chain),
+// all three UNWRAPPED; which group plays which role is the chain's own business:
+//   x   current state (wrapped where it is read)
+//   y   first-stage proposal (a large step: the uniforms themselves)
+//   z   second-stage proposal
+// A chain adopts a proposal by exchanging the roles of two of its groups (DRMLTSampler::accept without the copy): x_off and y_off
+// are PER LANE, the float offset of row 0 of the group with the chain's column folded in, each below 2^14 (64 KB of LDS); the z
+// group is the third one (the three offsets add up to `xyz`). Between loop sections a chain keeps the pair in one word (roles()).
 // Same arithmetic per component as LdsSampler (and Sampler): the chains are bit-identical.
 struct RowSampler {
     static constexpr bool batch_draws = true; // path_step: the (up to) five components of a step are read together, ahead of the hit's digestion
     uint32_t key0, key1;
     int mode, type;
     float sigma2;
-    uint32_t lane, stride, y_off, z_off;
+    uint32_t stride, x_off, y_off, xyz;
 
     DEV void reset_caches() {}
-    DEV float x(uint32_t k) const { return lds_x[k * stride + lane]; }
-    DEV float y_raw(uint32_t k) const { return lds_x[y_off + k * stride + lane]; }
-    DEV float z_raw(uint32_t k) const { return lds_x[z_off + k * stride + lane]; }
+    DEV float x(uint32_t k) const { return wrap01(lds_x[x_off + k * stride]); }
+    DEV float y_raw(uint32_t k) const { return lds_x[y_off + k * stride]; }
+    DEV uint32_t z_off() const { return xyz - x_off - y_off; }
+    DEV float z_raw(uint32_t k) const { return lds_x[z_off() + k * stride]; }
     DEV float next(uint32_t k) const {
         FP_STRICT;
         float v = y_raw(k);
@@ -323,14 +334,26 @@ struct RowSampler {
         }
         return wrap01(v);
     }
-    // first-stage proposal of chain column `col`, dimensions 4b .. 4b+3, from Philox block b of (major, chain)
-    DEV void fill_first(uint32_t col, uint32_t b, uint32_t major, uint32_t chain, bool large) const {
+    // adopt the first- (SM_STAGE1) or second-stage (SM_STAGE2) proposal: its group becomes x, the old x group is free for the
+    // next proposal of that stage (0: nothing adopted)
+    DEV void adopt(int commit_mode) {
+        const uint32_t xo = x_off, zo = z_off();
+        x_off = commit_mode == SM_STAGE1 ? y_off : (commit_mode == SM_STAGE2 ? zo : xo);
+        y_off = commit_mode == SM_STAGE1 ? xo : y_off;
+    }
+    // The two offsets in one word: what a chain lane keeps across loop sections, and what travels to the lanes that fill ANOTHER
+    // chain's rows in the flattened passes (bit 0 is free for the large-step bit there). `col`: the chain's column.
+    DEV uint32_t roles() const { return (x_off << 1) | (y_off << 16); }
+    DEV void set_roles(uint32_t w, uint32_t group, uint32_t col) { x_off = (w >> 1) & 0x7fffu; y_off = w >> 16; xyz = 3u * (group + col); }
+    DEV static uint32_t first_roles(uint32_t group, uint32_t col) { return (col << 1) | ((group + col) << 16); }
+    // first-stage proposal of the chain whose offsets this sampler carries, dimensions 4b .. 4b+3, from Philox block b of (major, chain)
+    DEV void fill_first(uint32_t b, uint32_t major, uint32_t chain, bool large) const {
         FP_STRICT;
         const u4 r = philox4x32_10(key0, key1, b, major, chain, TAG_S1);
         const float u0 = u32_to_unit(r.x), u1 = u32_to_unit(r.y), u2 = u32_to_unit(r.z), u3 = u32_to_unit(r.w);
-        const float *xs = &lds_x[4u * b * stride + col];
-        float *ys = &lds_x[y_off + 4u * b * stride + col];
-        const float x0 = xs[0], x1 = xs[stride], x2 = xs[2u * stride], x3 = xs[3u * stride];
+        const float *xs = &lds_x[x_off + 4u * b * stride];
+        float *ys = &lds_x[y_off + 4u * b * stride];
+        const float x0 = wrap01(xs[0]), x1 = wrap01(xs[stride]), x2 = wrap01(xs[2u * stride]), x3 = wrap01(xs[3u * stride]);
         float y0, y1, y2, y3;
         if (type == 2) { // pairwise orbital: radius from the Kelemen kernel (x 1.9), uniform angle (drmlt_sampler.cpp:354-361)
             const float d0 = kelemen_sample(u0, KELEMEN_S2 * ORBITAL_SCALE), d1 = kelemen_sample(u2, KELEMEN_S2 * ORBITAL_SCALE);
@@ -342,18 +365,19 @@ struct RowSampler {
         }
         ys[0] = large ? u0 : y0; ys[stride] = large ? u1 : y1; ys[2u * stride] = large ? u2 : y2; ys[3u * stride] = large ? u3 : y3;
     }
-    // second-stage proposal of chain column `col` from Philox block b of the TAG_S2 stream: a large step (timidAfterLarge)
+    // second-stage proposal of that chain from Philox block b of the TAG_S2 stream: a large step (timidAfterLarge)
     // -> dims 4b..4b+3 (uniforms); orbital -> the angles of pairs 4b..4b+3 = dims 8b..8b+7; iid kernels -> the Gaussian
     // perturbations of dims 2b, 2b+1 (draws 2k, 2k+1 belong to dim k). Blocks beyond the chain's kind of stage do nothing.
-    DEV void fill_second(uint32_t col, uint32_t b, uint32_t D4, uint32_t major, uint32_t chain, bool large) const {
+    DEV void fill_second(uint32_t b, uint32_t D4, uint32_t major, uint32_t chain, bool large) const {
         FP_STRICT;
         const uint32_t nblk = large ? D4 / 4u : (type == 2 ? (D4 / 2u + 3u) / 4u : D4 / 2u);
         if (b >= nblk) return;
         const u4 r = philox4x32_10(key0, key1, b, major, chain, TAG_S2);
         const float u[4] = {u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)};
+        const uint32_t zo = z_off();
         if (large) {
 #pragma unroll
-            for (uint32_t i = 0; i < 4u; ++i) lds_x[z_off + (4u * b + i) * stride + col] = u[i];
+            for (uint32_t i = 0; i < 4u; ++i) lds_x[zo + (4u * b + i) * stride] = u[i];
         } else if (type == 2) {
             // (all reads first: the writes below are to LDS too and may alias them for the compiler -- pair after pair would wait for its
             // own reads behind the previous pair's writes)
@@ -361,8 +385,8 @@ struct RowSampler {
 #pragma unroll
             for (uint32_t i = 0; i < 4u; ++i) {
                 const uint32_t k0 = 2u * (4u * b + i), kk = k0 + 1u < D4 ? k0 : 0u;
-                xa[i] = lds_x[kk * stride + col]; xb[i] = lds_x[(kk + 1u) * stride + col];
-                ya[i] = lds_x[y_off + kk * stride + col]; yb[i] = lds_x[y_off + (kk + 1u) * stride + col];
+                xa[i] = x(kk); xb[i] = x(kk + 1u);
+                ya[i] = y_raw(kk); yb[i] = y_raw(kk + 1u);
             }
 #pragma unroll
             for (uint32_t i = 0; i < 4u; ++i) {
@@ -376,15 +400,15 @@ struct RowSampler {
                     const float A = fminf(1.f, fmaxf(-1.f, (V + WC_DISPERSION) / (1.f + WC_DISPERSION * V)));
                     const float ct = A, st = sign * sqrtf(fmaxf(0.f, 1.f - A * A));
                     const float dx0 = x0 - y0, dx1 = x1 - y1;
-                    lds_x[z_off + k0 * stride + col] = y0 + (ct * dx0 - st * dx1);
-                    lds_x[z_off + (k0 + 1u) * stride + col] = y1 + (st * dx0 + ct * dx1);
+                    lds_x[zo + k0 * stride] = y0 + (ct * dx0 - st * dx1);
+                    lds_x[zo + (k0 + 1u) * stride] = y1 + (st * dx0 + ct * dx1);
                 }
             }
         } else {
             const uint32_t k = 2u * b;
-            const float x0 = lds_x[k * stride + col], x1 = lds_x[(k + 1u) * stride + col];
-            lds_x[z_off + k * stride + col] = x0 + gaussian_sample(u[0], u[1], sigma2);
-            lds_x[z_off + (k + 1u) * stride + col] = x1 + gaussian_sample(u[2], u[3], sigma2);
+            const float x0 = x(k), x1 = x(k + 1u);
+            lds_x[zo + k * stride] = x0 + gaussian_sample(u[0], u[1], sigma2);
+            lds_x[zo + (k + 1u) * stride] = x1 + gaussian_sample(u[2], u[3], sigma2);
         }
     }
 };

@@ -492,10 +492,11 @@ DEV void v4_flush(const DParams &P, const V4Lds &L, uint32_t &qn, uint32_t lane)
 // Everything wave-uniform that k_mutate_v4 derives from the parameter block: recomputed (a handful of scalar ops) by each
 // loop section from its own copy of the block, so that none of it occupies scalar registers across sections.
 struct V4Layout {
-    RowSampler smp;  // uniform fields only; `mode` and `lane` are per lane
+    RowSampler smp;  // uniform fields only; `mode` and the group offsets are per lane (set_roles)
     V4Lds L;
     LdsTables LT;
     uint32_t D, D4, nb1;
+    uint32_t group; // floats of one row group; the groups are at 0, group, 2 * group
 };
 DEV V4Layout v4_layout(const DParams &P, uint32_t qcap) {
     V4Layout Y;
@@ -504,14 +505,19 @@ DEV V4Layout v4_layout(const DParams &P, uint32_t qcap) {
     Y.D4 = (Y.D + 3u) & ~3u;
     Y.nb1 = Y.D4 / 4u; // first-stage Philox blocks of a mutation; item nb1 of a chain = the coins of its NEXT mutation
     Y.smp.key0 = P.key0; Y.smp.key1 = P.key1;
-    Y.smp.mode = SM_STAGE1; Y.smp.type = P.type; Y.smp.sigma2 = P.sigma2; Y.smp.lane = 0u;
+    Y.smp.mode = SM_STAGE1; Y.smp.type = P.type; Y.smp.sigma2 = P.sigma2;
     Y.smp.stride = V4_STRIDE;
-    Y.smp.y_off = Y.D * V4_STRIDE;
-    Y.smp.z_off = Y.smp.y_off + Y.D4 * V4_STRIDE;
-    Y.L.coin_off = Y.smp.z_off + Y.D4 * V4_STRIDE;
+    Y.smp.x_off = Y.smp.y_off = Y.smp.xyz = 0u;
+    Y.group = Y.D4 * V4_STRIDE;
+    Y.L.coin_off = 3u * Y.group;
     Y.L.list_off = Y.L.coin_off + 4u * V4_STRIDE;
     Y.L.q_off = Y.L.list_off + 32u;
-    Y.LT.shade_off = (Y.L.q_off + 5u * qcap + 3u) & ~3u;
+    // v4_lds_bytes counts D rows for one of the groups (the plan and the waves per CU are those of a D-row x group): the D4 - D
+    // rows it lacks, at most 99 floats, come out of the five queue rows -- 140 entries at least (BVH scenes: 80), 64 of them free
+    // at the head of every bookkeeping branch
+    const uint32_t q_floats = 5u * qcap - (Y.D4 - Y.D) * V4_STRIDE;
+    Y.L.qcap = q_floats / 5u;
+    Y.LT.shade_off = (Y.L.q_off + q_floats + 3u) & ~3u;
     Y.LT.bsdf_off = Y.LT.shade_off + (uint32_t) P.n_shade * 16u;
     Y.LT.emit_off = Y.LT.bsdf_off + (uint32_t) P.n_bsdfs * 12u;
     return Y;
@@ -532,7 +538,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
     const uint32_t cc = c < P.n_chains ? c : P.n_chains - 1;
     const uint32_t S = V4_STRIDE;
     constexpr uint32_t QCAP = (FEAT & 8) ? V4_QCAP_BVH : V4_QCAP;
-    int smp_mode = SM_STAGE1; // per-lane part of the sampler (which proposal the path in flight reads)
+    int smp_mode = SM_STAGE1; // per-lane part of the sampler: which proposal the path in flight reads ...
+    uint32_t roles; // ... and which row groups of the chain hold x and y (RowSampler::roles); every launch starts from groups 0 and 1
     uint32_t qn = 0u;
     ChainState cs;
     float cum = 0.f; // cumulative weight of the current state since it was adopted
@@ -551,8 +558,11 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
     int rstate = 0; // ray of this lane: 0 none, 1 issued, 2 being traversed, 3 result waiting to be consumed
     {
         const V4Layout Y = v4_layout(P, QCAP);
-        if (!helper)
-            for (uint32_t k = 0; k < Y.D; ++k) lds_x[k * S + sub] = P.x[(size_t) k * P.n_chains + cc];
+        roles = RowSampler::first_roles(Y.group, sub);
+        if (!helper) {
+            for (uint32_t k = 0; k < Y.D; ++k) lds_x[k * S + sub] = unwrap01(P.x[(size_t) k * P.n_chains + cc]);
+            for (uint32_t k = Y.D; k < Y.D4; ++k) lds_x[k * S + sub] = 0.f; // padding rows: proposed and adopted with the rest, never consumed
+        }
         cs.cur.lum = P.cur_lum[cc]; cs.cur.px = P.cur_px[cc]; cs.cur.py = P.cur_py[cc];
         cs.cur.r = P.cur_r[cc]; cs.cur.g = P.cur_g[cc]; cs.cur.b = P.cur_b[cc];
         cs.y = cs.cur; cs.z = cs.cur;
@@ -598,35 +608,39 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
             const V4Layout Y = v4_layout(Pm, QCAP);
             const V4Lds &L = Y.L;
             RowSampler smp = Y.smp;
-            smp.lane = sub; smp.mode = smp_mode;
-            const uint32_t nb1 = Y.nb1, D4 = Y.D4, D = Y.D;
+            smp.set_roles(roles, Y.group, sub); smp.mode = smp_mode;
+            const uint32_t nb1 = Y.nb1, D4 = Y.D4;
             int *const lds_list = reinterpret_cast<int *>(&lds_x[L.list_off]);
             if (prio) __builtin_amdgcn_s_setprio(2);
-            if (qn + 96u > QCAP) { SECTION_PARAMS(Pf); v4_flush(Pf, L, qn, lane); } // room for this branch's splats (at most 3 per chain)
+            if (qn + 64u > L.qcap) { SECTION_PARAMS(Pf); v4_flush(Pf, L, qn, lane); } // room for this branch's splats (at most 2 per chain)
             // ---- decide (parked chain lanes): weights, commit mode, what the chain does next
             int commit = 0, kind = 0; // kind: 0 nothing / finished, 1 next mutation, 2 second stage, 3 Green's reverse
-            bool want0 = false, want1 = false, want2 = false;
-            float e0x = 0.f, e0y = 0.f, e0r = 0.f, e0g = 0.f, e0b = 0.f;
-            float e1x = 0.f, e1y = 0.f, e1r = 0.f, e1g = 0.f, e1b = 0.f;
-            float e2x = 0.f, e2y = 0.f, e2r = 0.f, e2g = 0.f, e2b = 0.f;
+            // A decided mutation queues at most two splats (mh_digest: an accepted first stage has no second, w2 = 0):
+            //   y adopted: {cur}    z adopted: {cur, y}    neither: {y, z}
+            // slot A = the current state when it is left, else y; slot B = y when z is adopted, else z
+            bool wantA = false, wantB = false;
+            float eAx = 0.f, eAy = 0.f, eAr = 0.f, eAg = 0.f, eAb = 0.f;
+            float eBx = 0.f, eBy = 0.f, eBr = 0.f, eBg = 0.f, eBb = 0.f;
             if (parked) {
                 const MhDigest o = mh_decide(Pm, cs, smp, ps, ct);
                 if (o.decided) {
                     cum += o.w.w0;
-                    const bool a1st = o.acc1, a2nd = o.acc2;
+                    const bool a1st = o.acc1, a2nd = o.acc2, adopt = a1st || a2nd;
                     // rejected proposals are splatted now, an adopted one carries its weight into `cum`
-                    want1 = !a1st && o.w.w1 > 0.f;
-                    e1x = cs.y.px; e1y = cs.y.py; e1r = cs.y.r * o.w.w1; e1g = cs.y.g * o.w.w1; e1b = cs.y.b * o.w.w1;
-                    want2 = !a2nd && o.w.w2 > 0.f;
-                    e2x = cs.z.px; e2y = cs.z.py; e2r = cs.z.r * o.w.w2; e2g = cs.z.g * o.w.w2; e2b = cs.z.b * o.w.w2;
-                    if (o.acc1 || o.acc2) {
-                        want0 = cum > 0.f;
-                        e0x = cs.cur.px; e0y = cs.cur.py; e0r = cs.cur.r * cum; e0g = cs.cur.g * cum; e0b = cs.cur.b * cum;
+                    const DSplat sb = select_splat(a2nd, cs.y, cs.z);
+                    const float wb = a2nd ? o.w.w1 : o.w.w2;
+                    wantB = !a1st && wb > 0.f;
+                    eBx = sb.px; eBy = sb.py; eBr = sb.r * wb; eBg = sb.g * wb; eBb = sb.b * wb;
+                    const DSplat sa = select_splat(adopt, cs.cur, cs.y);
+                    const float wa = adopt ? cum : o.w.w1;
+                    wantA = wa > 0.f;
+                    eAx = sa.px; eAy = sa.py; eAr = sa.r * wa; eAg = sa.g * wa; eAb = sa.b * wa;
+                    if (adopt) {
                         cum = a1st ? o.w.w1 : o.w.w2;
                         cs.cur = select_splat(a1st, cs.y, cs.z);
                         if (o.amap) { // acceptance map: a mark at the pixel of the state that was LEFT (the weights are all zero)
                             const f3 mc = mh_amap_colour(o.amap);
-                            want1 = true; e1x = e0x; e1y = e0y; e1r = mc.x; e1g = mc.y; e1b = mc.z;
+                            wantB = true; eBx = eAx; eBy = eAy; eBr = mc.x; eBg = mc.y; eBb = mc.z;
                         }
                     }
                     commit = mh_commit_mode(o);
@@ -634,37 +648,14 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                 kind = cs.stage < 0 ? 4 : (cs.stage == 1 ? 2 : 3); // 4: between mutations -- resolved below
             }
             kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
-            v4_enqueue(L, qn, want0, e0x, e0y, e0r, e0g, e0b);
-            v4_enqueue(L, qn, want1, e1x, e1y, e1r, e1g, e1b);
-            v4_enqueue(L, qn, want2, e2x, e2y, e2r, e2g, e2b);
+            v4_enqueue(L, qn, wantA, eAx, eAy, eAr, eAg, eAb);
+            v4_enqueue(L, qn, wantB, eBx, eBy, eBr, eBg, eBb);
             const unsigned long long m1 = STAMP();
 
-            // ---- commit (DRMLTSampler::accept: uCurrent = wrap(chosen proposal)), flattened: items (accepted chain j, row
-            // quad q), chain-minor so that a pass touches as many different chains (banks) as possible
-            const uint32_t cmask = (uint32_t) __ballot(commit != 0);
-            if (cmask) {
-                if (commit) lds_list[__builtin_amdgcn_mbcnt_lo(cmask, 0u)] = (int) sub;
-                const uint32_t n = (uint32_t) __popc(cmask), total = n * nb1;
-                const float rcp_n = 1.f / (float) n;
-                for (uint32_t base = 0u; base < total; base += 64u) {
-                    const uint32_t i = base + lane;
-                    const bool valid = i < total;
-                    const uint32_t ii = valid ? i : 0u;
-                    const uint32_t q = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - q * n;
-                    const uint32_t cj = (uint32_t) lds_list[j];
-                    const int mode_j = __shfl(commit, (int) cj, 64);
-                    if (valid) {
-                        const float *src = &lds_x[(mode_j == SM_STAGE1 ? smp.y_off : smp.z_off) + 4u * q * S + cj];
-                        float *dst = &lds_x[4u * q * S + cj];
-                        float v[4]; // (reads first: the writes may alias them for the compiler)
-#pragma unroll
-                        for (uint32_t r = 0; r < 4u; ++r) v[r] = src[(4u * q + r < D ? r : 0u) * S];
-#pragma unroll
-                        for (uint32_t r = 0; r < 4u; ++r)
-                            if (4u * q + r < D) dst[r * S] = wrap01(v[r]);
-                    }
-                }
-            }
+            // ---- commit (DRMLTSampler::accept: uCurrent = wrap(chosen proposal)): the chosen proposal's row group BECOMES the
+            // chain's x group -- nothing is copied, and the wrap happens where x is read
+            smp.adopt(commit);
+            roles = smp.roles();
             const unsigned long long m2 = STAMP();
 
             // ---- start (parked chain lanes): the coins of the mutation that begins were drawn with the previous one
@@ -684,7 +675,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
             RowSampler smg = Yg.smp;
             const uint32_t chain_base_g = Pg.chain_offset + blockIdx.x * 32u;
             const uint32_t maj_mine = base + cs.it; // the mutation in flight (cs.it counts the mutations decided in this launch)
-            const unsigned info = cs.large ? 1u : 0u;
+            const unsigned info = roles | (cs.large ? 1u : 0u); // the chain's x and y offsets + its large-step bit, for the lanes that fill its rows
             const uint32_t f1mask = (uint32_t) __ballot(kind == 1);
             if (f1mask) {
                 if (kind == 1) lds_list[__builtin_amdgcn_mbcnt_lo(f1mask, 0u)] = (int) sub;
@@ -698,8 +689,9 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                     const uint32_t cj = (uint32_t) lds_list[j];
                     const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
                     const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
+                    smg.set_roles(inf, Yg.group, cj);
                     if (valid) {
-                        if (b < nb1) smg.fill_first(cj, b, mj, chain_base_g + cj, inf != 0u);
+                        if (b < nb1) smg.fill_first(b, mj, chain_base_g + cj, (inf & 1u) != 0u);
                         else {
                             const u4 coins = philox4x32_10(Pg.key0, Pg.key1, 0u, mj + 1u, chain_base_g + cj, TAG_COIN);
                             float *dst = &lds_x[L.coin_off + cj];
@@ -723,7 +715,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                     const uint32_t cj = (uint32_t) lds_list[j];
                     const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
                     const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
-                    if (valid) smg.fill_second(cj, b, D4, mj, chain_base_g + cj, inf != 0u);
+                    smg.set_roles(inf, Yg.group, cj);
+                    if (valid) smg.fill_second(b, D4, mj, chain_base_g + cj, (inf & 1u) != 0u);
                 }
             }
             const unsigned long long m4 = STAMP();
@@ -766,7 +759,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                 if (!helper && ps.phase != PH_DONE && ps.phase != PH_IDLE) {
                     const V4Layout Y = v4_layout(Ps, QCAP);
                     RowSampler smp = Y.smp;
-                    smp.lane = sub; smp.mode = smp_mode;
+                    smp.set_roles(roles, Y.group, sub); smp.mode = smp_mode;
                     if constexpr (FEAT == 0 && LDS_TABLES) path_step_diffuse(Ps, Y.LT, ps, smp, h, occluded == 0u, sr); // diffuse polygons: straight-line step
                     else if (LDS_TABLES) path_step<true, FEAT, RowSampler, LdsTables, false>(Ps, Y.LT, ps, smp, h, occluded == 0u, sr);
                     else path_step<true, FEAT, RowSampler, GlobalTables, false>(Ps, GlobalTables{Ps.shade, Ps.bsdfs, Ps.emitters}, ps, smp, h, occluded == 0u, sr);
@@ -812,7 +805,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                     rstate = 0;
                     const V4Layout Y = v4_layout(Ps, QCAP);
                     RowSampler smp = Y.smp;
-                    smp.lane = sub; smp.mode = smp_mode;
+                    smp.set_roles(roles, Y.group, sub); smp.mode = smp_mode;
                     if (LDS_TABLES) path_step<true, FEAT, RowSampler, LdsTables, false>(Ps, Y.LT, ps, smp, h, occluded == 0u, sr);
                     else path_step<true, FEAT, RowSampler, GlobalTables, false>(Ps, GlobalTables{Ps.shade, Ps.bsdfs, Ps.emitters}, ps, smp, h, occluded == 0u, sr);
                     if (ps.phase == PH_CLOSEST) rstate = 1;
@@ -838,6 +831,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
     SECTION_PARAMS(Pe);
     // "Perform the last splat": the current states with what they have accumulated since they were adopted
     const V4Layout Y = v4_layout(Pe, QCAP);
+    if (qn + 32u > Y.L.qcap) v4_flush(Pe, Y.L, qn, lane); // (the last branch may have left fewer than 32 entries free)
     v4_enqueue(Y.L, qn, live && cum > 0.f, cs.cur.px, cs.cur.py, cs.cur.r * cum, cs.cur.g * cum, cs.cur.b * cum);
     v4_flush(Pe, Y.L, qn, lane);
     if (stamps && lane == 0) {
@@ -848,7 +842,9 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
     }
 
     if (live) {
-        for (uint32_t k = 0; k < Y.D; ++k) Pe.x[(size_t) k * Pe.n_chains + c] = lds_x[k * S + sub];
+        RowSampler smp = Y.smp;
+        smp.set_roles(roles, Y.group, sub);
+        for (uint32_t k = 0; k < Y.D; ++k) Pe.x[(size_t) k * Pe.n_chains + c] = smp.x(k); // the wrap the commit used to do
         Pe.cur_lum[c] = cs.cur.lum; Pe.cur_px[c] = cs.cur.px; Pe.cur_py[c] = cs.cur.py;
         Pe.cur_r[c] = cs.cur.r; Pe.cur_g[c] = cs.cur.g; Pe.cur_b[c] = cs.cur.b;
         if (Pe.chain_done) Pe.chain_done[c] = base + cs.it;

@@ -14,7 +14,7 @@
 
 // ---- LDS layout constants and formulas (kernels.hip, kernels_mmlt.hip, kernels_bdpt.hip)
 constexpr uint32_t V4_STRIDE = 33u;   // row stride of the sampler rows: (row + chain) mod 32 banks serve per-chain AND per-dimension access patterns
-constexpr uint32_t V4_QCAP = 160u;    // splat queue entries: flushed when a bookkeeping branch (at most 3 x 32 new entries) might not fit
+constexpr uint32_t V4_QCAP = 160u;    // splat queue entries: flushed when a bookkeeping branch (at most 2 x 32 new entries) might not fit
 constexpr uint32_t V4_QCAP_BVH = 100u; // BVH scenes: their kernel also keeps the traversal stack in LDS (6 KB); flushes are a negligible part of it
 constexpr uint32_t V5_QCAP = 96u;     // splat queue entries (a round of the bookkeeping branch adds at most 64: flushed in between)
 constexpr uint32_t V5_QCAP_STACK32 = 0u; // the builds with 32-bit traversal stacks splat straight from the bookkeeping branch: their LDS goes to the stack column
@@ -25,6 +25,8 @@ constexpr int bdpt_eval_lds_floats(int max_depth) { return (2 * (2 * max_depth +
 
 // dynamic LDS bytes per wave (+ the scene tables, when they are staged)
 inline size_t v3_lds_bytes(size_t D) { return (D + 2 * ((D + 3) & ~(size_t) 3)) * 32 * sizeof(float); }
+// (k_mutate_v4: three row groups of D4 = D rounded up to 4 rows each; the D4 - D rows this formula does not count are taken from
+// the queue rows, which are up to 20 entries shorter than `qcap` -- v4_layout, kernels.hip)
 inline size_t v4_lds_bytes(size_t D, size_t qcap) { return ((D + 2 * ((D + 3) & ~(size_t) 3) + 4) * V4_STRIDE + 32 + 5 * qcap + 3) / 4 * 4 * sizeof(float); }
 inline size_t v5_lds_bytes(uint32_t D, uint32_t qcap, bool coin_rows) { return ((size_t) D * 64u + (coin_rows ? 4u * 64u : 0u) + 64u + 5u * qcap + 8u * V5_SLOTS + 2u * (V5_SLOTS / 4u)) * sizeof(float); }
 inline size_t mmlt_lds_bytes(int mmlt_S, int mmlt_E, int max_depth) { return ((size_t) mmlt_S + mmlt_E + 1 + 3 * ((size_t) max_depth + 3)) * 64 * sizeof(float); }
