@@ -14,6 +14,7 @@
 //   processMixture                            :161-380
 #pragma once
 #include "device_math.h"
+#include "device_types.h"
 
 DEV bool lum_invalid(float x) { return isnan(x) || isinf(x) || x <= 0.f; }        // drmlt_proc.cpp:428
 DEV bool lum_invalid_mix(float x) { return isnan(x) || isinf(x) || x < 0.f; }     // drmlt_proc.cpp:181
@@ -144,22 +145,27 @@ struct MhDigest {
 // needs it: after a large step both proposals are uniform (ratio 1), and with min(1, y/z) >= 1 the rule rejects without it.
 // Counts the decided mutation (and every reverse evaluation) in `ct`; the mutation counter, the sampler state and the splats
 // belong to the caller.
-template <class MiraRatio>
+// RULE (device_types.h): under RULE_ORBITAL the rule switches are compile-time constants -- mix, amap and the Green / Mira arms are
+// dead code, `stage` never reaches 2 -- and R's mix / amap / type are not read; the default compiles to the generic routine.
+template <int RULE = RULE_GENERIC, class MiraRatio>
 DEV MhDigest mh_digest(const MhRules R, bool large, float coin_acc1, float coin_acc2, float coin_mix, float lum, float cur_lum,
                        float y_lum, float z_lum, float &a1, int &stage, Counters &ct, MiraRatio mira_ratio) {
+    constexpr bool orbital = RULE == RULE_ORBITAL;
+    const bool mix = orbital ? false : R.mix, amap = orbital ? false : R.amap;
+    const int type = orbital ? 2 : R.type;
     MhDigest d{false, false, false, AMAP_NONE, {0.f, 0.f, 0.f}};
     float a2 = 0.f;
     if (stage == 0) {
         bool do_second = false;
-        mh_first(R.mix, R.timid_after_large, large, lum, cur_lum, coin_acc1, coin_mix, a1, d.acc1, do_second);
+        mh_first(mix, R.timid_after_large, large, lum, cur_lum, coin_acc1, coin_mix, a1, d.acc1, do_second);
         if (do_second) { d.acc1 = false; stage = 1; return d; }
-    } else if (stage == 1) {
-        if (R.mix) {
+    } else if (orbital || stage == 1) {
+        if (mix) {
             a1 = 0.f; // the second proposal replaces the first
             mh_second_mixture(lum, cur_lum, coin_acc2, a2, d.acc2);
         } else if (!lum_invalid(lum)) {
-            if (R.type == 0) { stage = 2; return d; } // Green: evaluate the reverse move first
-            if (R.type == 1) {
+            if (type == 0) { stage = 2; return d; } // Green: evaluate the reverse move first
+            if (type == 1) {
                 float ratio = 1.f;
                 if (!large && !(fminf(1.f, y_lum / lum) >= 1.f)) ratio = mira_ratio();
                 mh_second_mira(y_lum, lum, cur_lum, a1, ratio, coin_acc2, a2, d.acc2);
@@ -173,8 +179,8 @@ DEV MhDigest mh_digest(const MhRules R, bool large, float coin_acc1, float coin_
     }
     const bool do_second = stage != 0;
     d.decided = true;
-    d.w = mh_weights(R.mix, R.amap, do_second, a1, a2);
+    d.w = mh_weights(mix, amap, do_second, a1, a2);
     mh_count(ct, large, d.acc1, d.acc2, do_second);
-    d.amap = mh_amap_mark(R.mix, R.amap, large, d.acc1, d.acc2);
+    d.amap = mh_amap_mark(mix, amap, large, d.acc1, d.acc2);
     return d;
 }

@@ -313,7 +313,10 @@ struct LdsSampler {
 // are PER LANE, the float offset of row 0 of the group with the chain's column folded in, each below 2^14 (64 KB of LDS); the z
 // group is the third one (the three offsets add up to `xyz`). Between loop sections a chain keeps the pair in one word (roles()).
 // Same arithmetic per component as LdsSampler (and Sampler): the chains are bit-identical.
-struct RowSampler {
+// RULE (device_types.h): under RULE_ORBITAL `type` is 2 at compile time -- the fill routines keep their orbital arm, and `mode` is
+// SM_STAGE1 or SM_STAGE2 (the reverse move is Green's), so a component is ONE read, of y or of z.
+template <int RULE = RULE_GENERIC> struct RowSamplerT {
+    static constexpr bool orbital = RULE == RULE_ORBITAL;
     static constexpr bool batch_draws = true; // path_step: the (up to) five components of a step are read together, ahead of the hit's digestion
     uint32_t key0, key1;
     int mode, type;
@@ -327,6 +330,7 @@ struct RowSampler {
     DEV float z_raw(uint32_t k) const { return lds_x[z_off() + k * stride]; }
     DEV float next(uint32_t k) const {
         FP_STRICT;
+        if constexpr (orbital) return wrap01(lds_x[(mode == SM_STAGE1 ? y_off : z_off()) + k * stride]);
         float v = y_raw(k);
         if (mode != SM_STAGE1) {
             const float z = z_raw(k);
@@ -355,7 +359,7 @@ struct RowSampler {
         float *ys = &lds_x[y_off + 4u * b * stride];
         const float x0 = wrap01(xs[0]), x1 = wrap01(xs[stride]), x2 = wrap01(xs[2u * stride]), x3 = wrap01(xs[3u * stride]);
         float y0, y1, y2, y3;
-        if (type == 2) { // pairwise orbital: radius from the Kelemen kernel (x 1.9), uniform angle (drmlt_sampler.cpp:354-361)
+        if (orbital || type == 2) { // pairwise orbital: radius from the Kelemen kernel (x 1.9), uniform angle (drmlt_sampler.cpp:354-361)
             const float d0 = kelemen_sample(u0, KELEMEN_S2 * ORBITAL_SCALE), d1 = kelemen_sample(u2, KELEMEN_S2 * ORBITAL_SCALE);
             y0 = fmaf(d0, cos_rev(u1), x0); y1 = fmaf(d0, cos_rev(u1 - 0.25f), x1);
             y2 = fmaf(d1, cos_rev(u3), x2); y3 = fmaf(d1, cos_rev(u3 - 0.25f), x3);
@@ -370,7 +374,7 @@ struct RowSampler {
     // perturbations of dims 2b, 2b+1 (draws 2k, 2k+1 belong to dim k). Blocks beyond the chain's kind of stage do nothing.
     DEV void fill_second(uint32_t b, uint32_t D4, uint32_t major, uint32_t chain, bool large) const {
         FP_STRICT;
-        const uint32_t nblk = large ? D4 / 4u : (type == 2 ? (D4 / 2u + 3u) / 4u : D4 / 2u);
+        const uint32_t nblk = large ? D4 / 4u : ((orbital || type == 2) ? (D4 / 2u + 3u) / 4u : D4 / 2u);
         if (b >= nblk) return;
         const u4 r = philox4x32_10(key0, key1, b, major, chain, TAG_S2);
         const float u[4] = {u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)};
@@ -378,7 +382,7 @@ struct RowSampler {
         if (large) {
 #pragma unroll
             for (uint32_t i = 0; i < 4u; ++i) lds_x[zo + (4u * b + i) * stride] = u[i];
-        } else if (type == 2) {
+        } else if (orbital || type == 2) {
             // (all reads first: the writes below are to LDS too and may alias them for the compiler -- pair after pair would wait for its
             // own reads behind the previous pair's writes)
             float xa[4], xb[4], ya[4], yb[4];
@@ -412,6 +416,7 @@ struct RowSampler {
         }
     }
 };
+typedef RowSamplerT<> RowSampler;
 
 // ------------------------------------------------------------------ ray queries
 struct Hit {

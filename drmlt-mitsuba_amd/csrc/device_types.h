@@ -170,6 +170,20 @@ struct DParams {
     int32_t boot_weighted;       // bootstrap kernels: also write each sample's luminance under the importance map, to lum_out[n + i] (two-stage MLT: seeds drawn from the chains' own target, drmlt_capi.cpp)
 };
 
+// Compile-time rule tag of the chain loop (k_mutate_v4's bodies; mh_digest and RowSampler take it as a template parameter).
+//   RULE_GENERIC  every transition rule, selected by the run-time fields type / use_mixture / acceptance_map / timid_after_large
+//   RULE_ORBITAL  the pairwise orbital rule of the delayed-rejection loop alone. What mh_digest and mh_commit_mode read of the rule is
+//                 {mix, amap, timid_after_large, type}: the tag fixes type == 2 (so neither Green's reverse move nor Mira's ratio),
+//                 mix == false and amap == false; timid_after_large stays a run-time field (it only decides whether a rejected large
+//                 step gets a second stage, and then the uniform arm of fill_second).
+// rule_is_orbital is the ONE place the predicate is written down (constexpr: callable from host and device code); a context created
+// under DRMLT_RULE_GENERIC carries DBG_RULE_GENERIC in its debug mask and runs the generic body whatever its rule.
+enum { RULE_GENERIC = 0, RULE_ORBITAL = 1 };
+enum { DBG_RULE_GENERIC = 2048 };
+constexpr bool rule_is_orbital(const DParams &P) {
+    return P.type == 2 && P.use_mixture == 0 && P.acceptance_map == 0 && (P.debug & DBG_RULE_GENERIC) == 0;
+}
+
 // result of one PSS evaluation, SoA-friendly
 struct DSplat {
     float lum, px, py, r, g, b;

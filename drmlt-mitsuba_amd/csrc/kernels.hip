@@ -167,7 +167,8 @@ DEV int mh_commit_mode(const MhDigest &d) { return d.acc1 ? SM_STAGE1 : (d.acc2 
 
 // What the path kernels add to mh_digest: the evaluation's result comes out of a PathState and is normalised, the dimensions each
 // stage consumed are kept for Mira's ratio, and a decided mutation advances the chain's counter (stage -1: between mutations).
-template <class SamplerT> DEV MhDigest mh_decide(const DParams &P, ChainState &cs, SamplerT &smp, PathState &ps, Counters &ct) {
+// RULE_ORBITAL (k_mutate_v4's orbital body): mh_digest with the rule compiled in; nd1 / nd2, which only Mira's ratio reads, are not kept.
+template <int RULE = RULE_GENERIC, class SamplerT> DEV MhDigest mh_decide(const DParams &P, ChainState &cs, SamplerT &smp, PathState &ps, Counters &ct) {
     if (cs.stage < 0) return MhDigest{false, false, false, AMAP_NONE, {0.f, 0.f, 0.f}}; // nothing evaluated yet (first call of a launch)
     DSplat res;
     res.px = ps.px; res.py = ps.py; res.r = ps.Li.x; res.g = ps.Li.y; res.b = ps.Li.z;
@@ -177,10 +178,10 @@ template <class SamplerT> DEV MhDigest mh_decide(const DParams &P, ChainState &c
     // (selected VALUES: `if (stage == 0) cs.y = res; else if (stage == 1) cs.z = res;` is merged into one store through a selected
     // ADDRESS, and the chain state then lives in scratch memory -- see select_splat)
     const bool first = cs.stage == 0, second = cs.stage == 1;
-    cs.y = select_splat(first, res, cs.y); cs.nd1 = first ? ps.k : cs.nd1;
-    cs.z = select_splat(second, res, cs.z); cs.nd2 = second ? ps.k : cs.nd2;
+    cs.y = select_splat(first, res, cs.y); if constexpr (RULE != RULE_ORBITAL) cs.nd1 = first ? ps.k : cs.nd1;
+    cs.z = select_splat(second, res, cs.z); if constexpr (RULE != RULE_ORBITAL) cs.nd2 = second ? ps.k : cs.nd2;
     const MhRules R{P.use_mixture != 0, P.acceptance_map != 0, P.timid_after_large != 0, P.type};
-    const MhDigest d = mh_digest(R, cs.large, cs.coin_acc1, cs.coin_acc2, cs.coin_mix, res.lum, cs.cur.lum, cs.y.lum, cs.z.lum, cs.a1, cs.stage, ct,
+    const MhDigest d = mh_digest<RULE>(R, cs.large, cs.coin_acc1, cs.coin_acc2, cs.coin_mix, res.lum, cs.cur.lum, cs.y.lum, cs.z.lum, cs.a1, cs.stage, ct,
                                  [&]() { return mira_ratio(smp, cs.nd1, cs.nd2); });
     if (d.decided) { cs.it++; cs.stage = -1; }
     return d;
@@ -491,15 +492,15 @@ DEV void v4_flush(const DParams &P, const V4Lds &L, uint32_t &qn, uint32_t lane)
 // sixteen 64-bit wave-uniform accumulators would otherwise sit in (and spill from) the scalar registers of the real kernel.
 // Everything wave-uniform that k_mutate_v4 derives from the parameter block: recomputed (a handful of scalar ops) by each
 // loop section from its own copy of the block, so that none of it occupies scalar registers across sections.
-struct V4Layout {
-    RowSampler smp;  // uniform fields only; `mode` and the group offsets are per lane (set_roles)
+template <int RULE> struct V4Layout {
+    RowSamplerT<RULE> smp;  // uniform fields only; `mode` and the group offsets are per lane (set_roles)
     V4Lds L;
     LdsTables LT;
     uint32_t D, D4, nb1;
     uint32_t group; // floats of one row group; the groups are at 0, group, 2 * group
 };
-DEV V4Layout v4_layout(const DParams &P, uint32_t qcap) {
-    V4Layout Y;
+template <int RULE> DEV V4Layout<RULE> v4_layout(const DParams &P, uint32_t qcap) {
+    V4Layout<RULE> Y;
     Y.L.qcap = qcap;
     Y.D = (uint32_t) P.eff_dim;
     Y.D4 = (Y.D + 3u) & ~3u;
@@ -523,8 +524,20 @@ DEV V4Layout v4_layout(const DParams &P, uint32_t qcap) {
     return Y;
 }
 
-template <int FEAT, bool LDS_TABLES, bool STAMPS, bool STACK16 = false, bool OVF = false>
+// BUILD = FEAT | V4_ORBITAL_BUILD * RULE (device_types.h). The rule is fixed for a context's lifetime, so the builds that flat scenes
+// with their tables in LDS run (V4_F0, V4_F0_STAMPS, V4_F3, V4_F7) have a twin with the orbital rule compiled in, and
+// launch_mutate selects it once per launch by rule_is_orbital(P): no Build enumerator of its own, the plan is the same. The generic
+// kernels keep their names and their code. V4_F3_STAMPS, a diagnostic build, has none (its twin spills 54 scalar registers where
+// it spills 52: its stamps are those of the generic build). The BVH builds and the builds with their tables in device memory have no twin: their
+// time is in the traversal and in table fetches. stats[14] counts the waves that ran an orbital build (DRMLT_VERBOSE prints it with drmlt_stats_get).
+#define V4_ORBITAL_BUILD 16
+template <int BUILD, bool LDS_TABLES, bool STAMPS, bool STACK16 = false, bool OVF = false>
 __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n_mut, uint32_t mut_base) {
+    constexpr int FEAT = BUILD & (V4_ORBITAL_BUILD - 1), RULE = BUILD / V4_ORBITAL_BUILD;
+    typedef RowSamplerT<RULE> RowSampler;
+    typedef V4Layout<RULE> V4Layout;
+    constexpr bool orbital = RULE == RULE_ORBITAL; // stage 2 (Green's reverse move, kind 3, SM_REVERSE) does not occur
+    if (orbital && threadIdx.x == 0) atomicAdd(P.stats + 14, 1ull);
     // The parameter block is ~80 dwords, most of it used by one loop section only. Left to itself the compiler loads every
     // field it will ever need before the loop and then spills scalar registers into vector lanes all through the loop
     // (a sixth of the kernel's VALU instructions were v_readlane / v_writelane). Each loop section therefore works on its
@@ -557,7 +570,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
     trav_reset_counters(T);
     int rstate = 0; // ray of this lane: 0 none, 1 issued, 2 being traversed, 3 result waiting to be consumed
     {
-        const V4Layout Y = v4_layout(P, QCAP);
+        const V4Layout Y = v4_layout<RULE>(P, QCAP);
         roles = RowSampler::first_roles(Y.group, sub);
         if (!helper) {
             for (uint32_t k = 0; k < Y.D; ++k) lds_x[k * S + sub] = unwrap01(P.x[(size_t) k * P.n_chains + cc]);
@@ -605,7 +618,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
         if (pmask && (__popcll(pmask) >= batch || !rmask)) {
             n_mh++;
             SECTION_PARAMS(Pm);
-            const V4Layout Y = v4_layout(Pm, QCAP);
+            const V4Layout Y = v4_layout<RULE>(Pm, QCAP);
             const V4Lds &L = Y.L;
             RowSampler smp = Y.smp;
             smp.set_roles(roles, Y.group, sub); smp.mode = smp_mode;
@@ -622,7 +635,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
             float eAx = 0.f, eAy = 0.f, eAr = 0.f, eAg = 0.f, eAb = 0.f;
             float eBx = 0.f, eBy = 0.f, eBr = 0.f, eBg = 0.f, eBb = 0.f;
             if (parked) {
-                const MhDigest o = mh_decide(Pm, cs, smp, ps, ct);
+                const MhDigest o = mh_decide<RULE>(Pm, cs, smp, ps, ct);
                 if (o.decided) {
                     cum += o.w.w0;
                     const bool a1st = o.acc1, a2nd = o.acc2, adopt = a1st || a2nd;
@@ -645,7 +658,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                     }
                     commit = mh_commit_mode(o);
                 }
-                kind = cs.stage < 0 ? 4 : (cs.stage == 1 ? 2 : 3); // 4: between mutations -- resolved below
+                kind = cs.stage < 0 ? 4 : ((orbital || cs.stage == 1) ? 2 : 3); // 4: between mutations -- resolved below
             }
             kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
             v4_enqueue(L, qn, wantA, eAx, eAy, eAr, eAg, eAb);
@@ -671,7 +684,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
             // ---- proposals of the chains that start a mutation, flattened: items (chain j, Philox block b) -> dimensions
             // 4b..4b+3 of y; block nb1 = the four coins (large step, first / second acceptance, mixture) of the NEXT mutation
             SECTION_PARAMS(Pg);
-            const V4Layout Yg = v4_layout(Pg, QCAP);
+            const V4Layout Yg = v4_layout<RULE>(Pg, QCAP);
             RowSampler smg = Yg.smp;
             const uint32_t chain_base_g = Pg.chain_offset + blockIdx.x * 32u;
             const uint32_t maj_mine = base + cs.it; // the mutation in flight (cs.it counts the mutations decided in this launch)
@@ -704,7 +717,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
             if (f2mask) { // second-stage proposals (rare: rejected bold steps)
                 if (kind == 2) lds_list[__builtin_amdgcn_mbcnt_lo(f2mask, 0u)] = (int) sub;
                 // blocks per chain: uniforms for a large step (one per dim), the orbital angles (one per pair), Gaussian pairs otherwise
-                const uint32_t nb2 = Pg.type == 2 ? (Pg.timid_after_large ? D4 / 4u : (D4 / 2u + 3u) / 4u) : D4 / 2u;
+                const uint32_t nb2 = (orbital || Pg.type == 2) ? (Pg.timid_after_large ? D4 / 4u : (D4 / 2u + 3u) / 4u) : D4 / 2u;
                 const uint32_t n = (uint32_t) __popc(f2mask), total = n * nb2;
                 const float rcp_n = 1.f / (float) n;
                 for (uint32_t base = 0u; base < total; base += 64u) {
@@ -726,7 +739,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                 if (kind == 0) ps.phase = PH_IDLE;
                 else {
                     SECTION_PARAMS(Pb);
-                    smp_mode = smp.mode = cs.stage == 0 ? SM_STAGE1 : (cs.stage == 1 ? SM_STAGE2 : SM_REVERSE);
+                    smp_mode = smp.mode = cs.stage == 0 ? SM_STAGE1 : ((orbital || cs.stage == 1) ? SM_STAGE2 : SM_REVERSE);
                     path_init(Pb, ps);
                     const float v0 = smp.next(0u), v1 = smp.next(1u);
                     path_begin(Pb, ps, v0, v1);
@@ -757,7 +770,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
             {
                 SECTION_PARAMS(Ps);
                 if (!helper && ps.phase != PH_DONE && ps.phase != PH_IDLE) {
-                    const V4Layout Y = v4_layout(Ps, QCAP);
+                    const V4Layout Y = v4_layout<RULE>(Ps, QCAP);
                     RowSampler smp = Y.smp;
                     smp.set_roles(roles, Y.group, sub); smp.mode = smp_mode;
                     if constexpr (FEAT == 0 && LDS_TABLES) path_step_diffuse(Ps, Y.LT, ps, smp, h, occluded == 0u, sr); // diffuse polygons: straight-line step
@@ -803,7 +816,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                 if (ready) {
                     h = T.h;
                     rstate = 0;
-                    const V4Layout Y = v4_layout(Ps, QCAP);
+                    const V4Layout Y = v4_layout<RULE>(Ps, QCAP);
                     RowSampler smp = Y.smp;
                     smp.set_roles(roles, Y.group, sub); smp.mode = smp_mode;
                     if (LDS_TABLES) path_step<true, FEAT, RowSampler, LdsTables, false>(Ps, Y.LT, ps, smp, h, occluded == 0u, sr);
@@ -830,7 +843,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
     // (state rows, film, counters) in scalar registers -- spilled -- all through the loop
     SECTION_PARAMS(Pe);
     // "Perform the last splat": the current states with what they have accumulated since they were adopted
-    const V4Layout Y = v4_layout(Pe, QCAP);
+    const V4Layout Y = v4_layout<RULE>(Pe, QCAP);
     if (qn + 32u > Y.L.qcap) v4_flush(Pe, Y.L, qn, lane); // (the last branch may have left fewer than 32 entries free)
     v4_enqueue(Y.L, qn, live && cum > 0.f, cs.cur.px, cs.cur.py, cs.cur.r * cum, cs.cur.g * cum, cs.cur.b * cum);
     v4_flush(Pe, Y.L, qn, lane);
@@ -1632,6 +1645,8 @@ void launch_init_chains(const DParams &P, const uint32_t *seed_index, const floa
 void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st) {
     if (plan.verbose && !plan.note.empty()) fprintf(stderr, "%s\n", plan.note.c_str());
 #define LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(plan.grid), dim3(CHAIN_BLOCK), plan.lds, st, P, n_mut, mut_base); break
+#define LAUNCH_RULE(FEAT, ...) if (orbital) { LAUNCH(k_mutate_v4<FEAT | V4_ORBITAL_BUILD, __VA_ARGS__>); } LAUNCH(k_mutate_v4<FEAT, __VA_ARGS__>)
+    const bool orbital = rule_is_orbital(P);
     switch (plan.build) {
     case Build::PSSMLT: LAUNCH(k_mutate_pssmlt);
     // k_mutate_v5 <FEAT, STACK16, OVF, STAMPS, LDS_TABLES, ROWS_MEM>: ray pool, 64 chains per wave
@@ -1647,8 +1662,9 @@ void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint
     case Build::V5_F8_OVF: LAUNCH(k_mutate_v5<8, true, true>);  case Build::V5_F15_OVF: LAUNCH(k_mutate_v5<15, true, true>);
     case Build::V5_F8_STAMPS: LAUNCH(k_mutate_v5<8, true, false, true>); case Build::V5_F8: LAUNCH(k_mutate_v5<8, true, false>); case Build::V5_F15: LAUNCH(k_mutate_v5<15, true, false>);
     // k_mutate_v4 <FEAT, LDS_TABLES, STAMPS, STACK16, OVF>: lane pairs, 32 chains per wave
-    case Build::V4_F0_STAMPS: LAUNCH(k_mutate_v4<0, true, true>); case Build::V4_F0: LAUNCH(k_mutate_v4<0, true, false>);
-    case Build::V4_F3_STAMPS: LAUNCH(k_mutate_v4<3, true, true>); case Build::V4_F3: LAUNCH(k_mutate_v4<3, true, false>); case Build::V4_F7: LAUNCH(k_mutate_v4<7, true, false>);
+    // (LAUNCH_RULE: the orbital twin of the build when the context's rule is the orbital one)
+    case Build::V4_F0_STAMPS: LAUNCH_RULE(0, true, true); case Build::V4_F0: LAUNCH_RULE(0, true, false);
+    case Build::V4_F3_STAMPS: LAUNCH(k_mutate_v4<3, true, true>); case Build::V4_F3: LAUNCH_RULE(3, true, false); case Build::V4_F7: LAUNCH_RULE(7, true, false);
     case Build::V4_F15_S32: LAUNCH(k_mutate_v4<15, true, false, false, true>); case Build::V4_F15_OVF: LAUNCH(k_mutate_v4<15, true, false, true, true>);
     case Build::V4_F15: LAUNCH(k_mutate_v4<15, true, false, true>);            case Build::V4_F7_GLOBAL: LAUNCH(k_mutate_v4<7, false, false>);
     case Build::V4_F8_S32_GLOBAL: LAUNCH(k_mutate_v4<8, false, false, false, true>); case Build::V4_F15_S32_GLOBAL: LAUNCH(k_mutate_v4<15, false, false, false, true>);
@@ -1661,6 +1677,7 @@ void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint
         fprintf(stderr, "[drmlt] launch_mutate: build %d is not a technique=path kernel\n", (int) plan.build);
         abort();
     }
+#undef LAUNCH_RULE
 #undef LAUNCH
 }
 void launch_eval_paths(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out8, hipStream_t st) {

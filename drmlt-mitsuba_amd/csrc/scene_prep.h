@@ -495,7 +495,7 @@ inline std::string prepare_scene(const drmlt_config &cfg, const drmlt_scene &sce
         P.eff_dim = P.mmlt_S + P.mmlt_E + P.bd_Dd;
     }
 
-    P.debug = K.debug;
+    P.debug = K.debug | (K.rule_generic ? DBG_RULE_GENERIC : 0);
     for (const DBsdf &b : out.bsdfs) P.features |= b.type == DRMLT_BSDF_ROUGHCONDUCTOR ? 1 : ((b.type == DRMLT_BSDF_DIELECTRIC || b.type == DRMLT_BSDF_CONDUCTOR) ? 2 : 0);
     for (const DPrim &g : out.prims) if (g.type == PRIM_SPHERE) P.features |= 4;
     P.env_emitter = -1;
