@@ -31,6 +31,10 @@ __host__ __device__ inline int mmlt_max_dim(int depth) {
 // configured maxDepth can consume: S = 2 (maxDepth + 1), E = 2 maxDepth). Draws of a (tag, mutation) stream:
 // sensor from index 0, emitter from 2 Dmax, direct from 4 Dmax, Dmax = mmlt_max_dim(maxDepth) -- the same
 // addressing as the oracle's MMLTSamplers, so chains are comparable mutation by mutation.
+// The orbital pair below is written out here and NOT built on device_sampler.h's leaf routines: it takes the pair's sine with
+// sin_rev (the path samplers: cos_rev(a - 0.25f)) and is compiled with the default contraction, not FP_STRICT, so moving it would
+// change mmlt and bdpt results in the last bit. Follow-up: move MSampler onto the leaves in a change of its own, with the oracle
+// parity of both techniques re-measured.
 struct MSampler {
     uint32_t key0, key1, chain, major;
     int mode, type;

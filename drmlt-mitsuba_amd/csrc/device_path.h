@@ -1,10 +1,7 @@
-// Device code of the DRMLT hot path: PSS samplers (transition kernels evaluated lazily as
-// pure functions of the addressed RNG), ray queries, and the unidirectional estimator as a
-// resumable state machine with exactly one ray query per step.
+// Device code of the DRMLT hot path: ray queries, the scene tables, and the unidirectional estimator as a
+// resumable state machine with exactly one ray query per step. (PSS transitions and samplers: device_sampler.h.)
 //
 // Reference behaviour restated here (paths relative to the reference checkout):
-//   transition kernels       src/integrators/drmlt/tools/transition.h:54-190
-//   fillSpace / wrap         src/integrators/drmlt/drmlt_sampler.cpp:313-394, drmlt_sampler.h:140-144
 //   sampleSplats (path)      src/libbidir/pathsampler.cpp:529-567
 //   MIPathTracer::Li         src/integrators/path/path.cpp:123-321
 //   ray epsilons             src/librender/skdtree.cpp:125-129,213-218, scene.cpp:891-893
@@ -14,409 +11,8 @@
 #pragma once
 #include "device_bsdf.h"
 #include "device_math.h"
+#include "device_sampler.h"
 #include "device_types.h"
-
-// Current PSS states of the 64 chains of this wave, [dim][lane]: lane-contiguous rows, so any
-// per-lane dimension pattern is bank-conflict free (64 == 0 mod 32 banks). Addressed directly
-// (ds_read), never through a generic pointer: LDS offset 0 casts to the flat null pointer.
-extern __shared__ __attribute__((aligned(16))) float lds_x[];
-
-// The proposal arithmetic is evaluated at several sites (on demand in k_mutate / k_mutate_v2 / v3, for whole rows in
-// k_mutate_v4, pair-wise at a commit): without this the compiler contracts a*b+c into an fma at some sites and not at
-// others, and the kernels' chains drift apart in the last bit. Explicit fmaf() calls stay fused everywhere.
-#define FP_STRICT _Pragma("clang fp contract(off)")
-
-// ------------------------------------------------------------------ PSS sampler
-enum { SM_BOOT = 0, SM_ARRAY = 1, SM_STAGE1 = 2, SM_STAGE2 = 3, SM_REVERSE = 4, SM_PT = 5 };
-
-// drmlt_sampler.h:140-144: y > 1 ? 2 - y : (y <= 0 ? |y| : y). For 0 < y <= 1, |y| = y, so two selects collapse into
-// one select on an |.|-modified operand (the nested form compiled to two exec-mask branches per component).
-DEV float wrap01(float y) { return y > 1.f ? 2.f - y : fabsf(y); }
-// A value that wrap01 maps back onto v, bit for bit, for every v that wrap01 returns: v itself inside [0, 1] (and for a NaN),
-// where wrap01 is the identity; outside -- perturbations of more than one, which no sane setting produces -- v > 1 came from -v,
-// and v < 0 from 2 - v (an exact difference: y >= 2 is a multiple of 2^-22, and so is 2 - y). Checked over all 2^32 arguments
-// of wrap01: one exception, y = 2^25 + 4, where 2 - y is a rounding tie. k_mutate_v4 keeps its current state unwrapped and
-// wraps it where it is read; it loads a stored (wrapped) state through this.
-DEV float unwrap01(float v) { return v < 0.f ? 2.f - v : (v > 1.f ? -v : v); }
-
-#define KELEMEN_S1 (1.0f / 1024.0f)
-#define KELEMEN_S2 (1.0f / 64.0f)
-#define ORBITAL_SCALE 1.9f
-#define LOG2_S1_OVER_S2 (-4.0f) // log2((1/1024)/(1/64))
-// wrapped Cauchy: rho = exp(-1/4), dispersion c = 2 rho / (1 + rho^2)
-#define WC_DISPERSION 0.96954361f
-
-// Kelemen kernel (transition.h:97-111): sign * s2 * (s1/s2)^(1 - xi')
-DEV float kelemen_sample(float xi, float s2) {
-        FP_STRICT;
-    float sign = 1.f;
-    if (xi < 0.5f) { xi *= 2.f; } else { sign = -1.f; xi = 2.f * (xi - 0.5f); }
-    return sign * s2 * fast_exp2((1.f - xi) * LOG2_S1_OVER_S2);
-}
-// Gaussian kernel (transition.h:61-66), Box-Muller cosine branch
-DEV float gaussian_sample(float u1, float u2, float sigma) {
-        FP_STRICT;
-    float tmp = sqrtf(-1.3862943611198906f * fast_log2(1.f - u1)); // -2 ln(v) = -2 ln2 log2(v)
-    return tmp * cos_rev(u2) * sigma;
-}
-// log pdf of the (unscaled) Kelemen kernel, transition.h:113-122
-// (a select, not an early return: in an unrolled ratio loop every return was an exec mask kept in scalar registers)
-DEV float kelemen_logpdf(float du) {
-    float d = fabsf(du);
-    const float l = -__logf(2.f * d * 2.772588722239781f); // ln(s2/s1) = ln 16
-    return (d < KELEMEN_S1 || d > KELEMEN_S2) ? -INFINITY : l;
-}
-
-// STRIDE: floats per row of the chain-state rows in LDS (x[k] of the chain in column `lane` = lds_x[k * STRIDE + lane])
-template <uint32_t STRIDE = 64u> struct SamplerT {
-    // addressing
-    uint32_t key0, key1, chain, major; // major: mutation index (chains) or sample index (boot / pt)
-    int mode, type;
-    bool large;
-    float sigma2;
-    uint32_t lane;    // chain state lives in LDS: x[k] = lds_x[k * 64 + lane]
-    const float *arr; // SM_ARRAY: explicit PSS vector
-    // one-block caches
-    u4 b1, b2;
-    uint32_t b1_idx, b2_idx;
-    // orbital pair cache
-    uint32_t pair_base;
-    float pair_y0, pair_y1, pair_z0, pair_z1;
-    bool pair_has_z;
-
-    DEV void reset_caches() { b1_idx = b2_idx = 0xffffffffu; pair_base = 0xffffffffu; }
-
-    DEV float u_boot(uint32_t k, uint32_t tag) {
-        uint32_t blk = k >> 2;
-        if (blk != b1_idx) { b1 = philox4x32_10(key0, key1, blk, major, chain, tag); b1_idx = blk; }
-        return pick4(b1, k & 3u);
-    }
-    DEV float u_s1(uint32_t idx) {
-        uint32_t blk = idx >> 2;
-        if (blk != b1_idx) { b1 = philox4x32_10(key0, key1, blk, major, chain, TAG_S1); b1_idx = blk; }
-        return pick4(b1, idx & 3u);
-    }
-    DEV float u_s2(uint32_t idx) {
-        uint32_t blk = idx >> 2;
-        if (blk != b2_idx) { b2 = philox4x32_10(key0, key1, blk, major, chain, TAG_S2); b2_idx = blk; }
-        return pick4(b2, idx & 3u);
-    }
-    DEV float x(uint32_t k) const { return lds_x[k * STRIDE + lane]; }
-
-    // first-stage proposal, unwrapped (fillSpace with isFirst = true)
-    DEV float y_raw(uint32_t k) {
-        FP_STRICT;
-        if (large) return u_s1(k);
-        if (type != 2 /*orbital*/) return x(k) + kelemen_sample(u_s1(k), KELEMEN_S2);
-        ensure_pair(k & ~1u, false);
-        return (k & 1u) ? pair_y1 : pair_y0;
-    }
-    // second-stage proposal, unwrapped (fillSpace with isFirst = false)
-    DEV float z_raw(uint32_t k) {
-        FP_STRICT;
-        // second stage of a large step (timidAfterLarge): the reference's fillSpace takes its
-        // uniform branch again (drmlt_sampler.cpp:319-321 behind a debug-only assertion)
-        if (large) return u_s2(k);
-        if (type != 2) return x(k) + gaussian_sample(u_s2(2u * k), u_s2(2u * k + 1u), sigma2);
-        ensure_pair(k & ~1u, true);
-        return (k & 1u) ? pair_z1 : pair_z0;
-    }
-    // orbital pair (k0, k0+1): y = x + d (cos a, sin a); z = y + R(theta) (x - y)
-    DEV void ensure_pair(uint32_t k0, bool need_z) {
-        FP_STRICT;
-        if (pair_base != k0) {
-            pair_base = k0;
-            float x0 = x(k0), x1 = x(k0 + 1u);
-            if (large) {
-                pair_y0 = u_s1(k0);
-                pair_y1 = u_s1(k0 + 1u);
-            } else {
-                float d = kelemen_sample(u_s1(k0), KELEMEN_S2 * ORBITAL_SCALE);
-                float a = u_s1(k0 + 1u);
-                pair_y0 = fmaf(d, cos_rev(a), x0);
-                pair_y1 = fmaf(d, cos_rev(a - 0.25f), x1); // sin(2 pi a) as the row samplers evaluate it (v_sin and v_cos differ in the last bit)
-            }
-            pair_has_z = false;
-        }
-        if (need_z && !pair_has_z) {
-            pair_has_z = true;
-            float x0 = x(k0), x1 = x(k0 + 1u);
-            // theta ~ wrapped Cauchy by inverse CDF (transition.h:157-173): cos(theta) = A
-            float xi = u_s2(k0 >> 1);
-            float sign = 1.f;
-            if (xi < 0.5f) { xi *= 2.f; } else { sign = -1.f; xi = 2.f * (xi - 0.5f); }
-            float V = cos_rev(xi);
-            float A = fminf(1.f, fmaxf(-1.f, (V + WC_DISPERSION) / (1.f + WC_DISPERSION * V)));
-            float ct = A, st = sign * sqrtf(fmaxf(0.f, 1.f - A * A));
-            // (x - y) rotated by theta about y: identical to y + |x-y| (cos, sin)(theta + mu),
-            // mu the polar angle of x - y (drmlt_sampler.cpp:374-391), without the acos round trip
-            float dx0 = x0 - pair_y0, dx1 = x1 - pair_y1;
-            pair_z0 = pair_y0 + (ct * dx0 - st * dx1);
-            pair_z1 = pair_y1 + (st * dx0 + ct * dx1);
-        }
-    }
-
-    // value handed to the path code for PSS dimension k (primarySample)
-    DEV float next(uint32_t k) {
-        FP_STRICT;
-        switch (mode) {
-            case SM_BOOT: return u_boot(k, TAG_BOOT);
-            case SM_PT: return u_boot(k, TAG_PT);
-            case SM_ARRAY: return arr[k];
-            case SM_STAGE1: return wrap01(y_raw(k));
-            case SM_STAGE2: return wrap01(z_raw(k));
-            default: { // Green reverse: y* = z - (y - x)
-                float du = y_raw(k) - x(k);
-                return wrap01(z_raw(k) - du);
-            }
-        }
-    }
-};
-typedef SamplerT<64u> Sampler;
-
-// ------------------------------------------------------------------ PSS sampler of k_mutate_v2
-// Same proposals as `Sampler`, but the Philox draws of a mutation are produced up front, by all
-// lanes that start an evaluation together (convergent code in the bookkeeping branch), and parked
-// in LDS next to the chain state:
-//   lds_x  [0 .. D)          current state x
-//   lds_u1 = lds_x + D*64    first-stage uniforms, draw k of the TAG_S1 stream (row k, D rounded to 4)
-//   lds_s2 = lds_u1 + D4*64  second-stage values: orbital: theta uniform of pair q in row q;
-//                            iid: the Gaussian perturbation of dim k in row k; large: uniform k
-// The per-dimension code below is then pure arithmetic on LDS operands -- no RNG, no caches, no
-// divergent Philox in the ray loop (measured: the on-demand sampler was ~2/3 of the VALU work).
-struct LdsSampler {
-    uint32_t key0, key1, chain, major;
-    int mode, type;
-    bool large;
-    float sigma2;
-    uint32_t lane;
-    uint32_t u1_off, s2_off; // row offsets (in floats) of lds_u1 / lds_s2
-    uint32_t stride;         // floats per row (64; 32 in the half-wave experiment)
-    bool timing_probe;       // DRMLT_DEBUG bit 256: replace stage-1 Philox by a trivial hash (timing experiments only)
-
-    DEV void reset_caches() {}
-    DEV float x(uint32_t k) const { return lds_x[k * stride + lane]; }
-    DEV float u1(uint32_t k) const { return lds_x[u1_off + k * stride + lane]; }
-    DEV float s2(uint32_t k) const { return lds_x[s2_off + k * stride + lane]; }
-
-    // first-stage draws of this mutation, Philox blocks [b0, b1): rows 4b .. 4b+3 of lds_u1
-    DEV void fill_stage1(uint32_t b0, uint32_t b1) {
-        for (uint32_t b = b0; b < b1; ++b) {
-            u4 r = timing_probe ? u4{b * 2654435761u ^ major, chain * 40503u + b, major * 2246822519u, b + chain}
-                                : philox4x32_10(key0, key1, b, major, chain, TAG_S1);
-            float *dst = &lds_x[u1_off + b * 4u * stride + lane];
-            dst[0] = u32_to_unit(r.x); dst[stride] = u32_to_unit(r.y); dst[2u * stride] = u32_to_unit(r.z); dst[3u * stride] = u32_to_unit(r.w);
-        }
-    }
-    // second-stage values (see layout above); blocks first, first + step, ... (step 2 = shared by two lanes)
-    DEV void fill_stage2(uint32_t D4, uint32_t first, uint32_t step) {
-        FP_STRICT;
-        if (large || type == 2) {
-            const uint32_t rows = large ? D4 : (D4 / 2u + 3u) & ~3u; // uniforms: one per dim, or one per pair
-            for (uint32_t b = first; b < rows / 4u; b += step) {
-                u4 r = philox4x32_10(key0, key1, b, major, chain, TAG_S2);
-                float *dst = &lds_x[s2_off + b * 4u * stride + lane];
-                dst[0] = u32_to_unit(r.x); dst[stride] = u32_to_unit(r.y); dst[2u * stride] = u32_to_unit(r.z); dst[3u * stride] = u32_to_unit(r.w);
-            }
-        } else {
-            for (uint32_t b = first; b < D4 / 2u; b += step) { // draws (2k, 2k+1) -> Gaussian sample of dim k
-                u4 r = philox4x32_10(key0, key1, b, major, chain, TAG_S2);
-                float *dst = &lds_x[s2_off + b * 2u * stride + lane];
-                dst[0] = gaussian_sample(u32_to_unit(r.x), u32_to_unit(r.y), sigma2);
-                dst[stride] = gaussian_sample(u32_to_unit(r.z), u32_to_unit(r.w), sigma2);
-            }
-        }
-    }
-
-    DEV float y_raw(uint32_t k) const {
-        FP_STRICT;
-        if (large) return u1(k);
-        if (type != 2) return x(k) + kelemen_sample(u1(k), KELEMEN_S2);
-        const uint32_t k0 = k & ~1u;
-        float d = kelemen_sample(u1(k0), KELEMEN_S2 * ORBITAL_SCALE), a = u1(k0 + 1u);
-        return fmaf(d, cos_rev(a - ((k & 1u) ? 0.25f : 0.f)), x(k));
-    }
-    DEV float z_raw(uint32_t k) const {
-        FP_STRICT;
-        if (large) return s2(k);
-        if (type != 2) return x(k) + s2(k);
-        const uint32_t k0 = k & ~1u;
-        float x0 = x(k0), x1 = x(k0 + 1u);
-        float d = kelemen_sample(u1(k0), KELEMEN_S2 * ORBITAL_SCALE), a = u1(k0 + 1u);
-        float y0 = fmaf(d, cos_rev(a), x0), y1 = fmaf(d, cos_rev(a - 0.25f), x1);
-        float xi = s2(k0 >> 1);
-        float sign = 1.f;
-        if (xi < 0.5f) { xi *= 2.f; } else { sign = -1.f; xi = 2.f * (xi - 0.5f); }
-        float V = cos_rev(xi);
-        float A = fminf(1.f, fmaxf(-1.f, (V + WC_DISPERSION) / (1.f + WC_DISPERSION * V)));
-        float ct = A, st = sign * sqrtf(fmaxf(0.f, 1.f - A * A));
-        float dx0 = x0 - y0, dx1 = x1 - y1;
-        return (k & 1u) ? y1 + (st * dx0 + ct * dx1) : y0 + (ct * dx0 - st * dx1);
-    }
-    DEV float next(uint32_t k) const {
-        FP_STRICT;
-        if (type == 2 && mode == SM_STAGE1) {
-            // The common case (orbital, first stage) without divergent branches: unconditional LDS reads, the
-            // large-step case as a select, sin(2 pi a) as cos(2 pi (a - 1/4)) so that one v_cos serves both components.
-            const uint32_t k0 = k & ~1u;
-            const bool odd = (k & 1u) != 0u;
-            const float ua = u1(k0), ub = u1(k0 + 1u);
-            const float d = kelemen_sample(ua, KELEMEN_S2 * ORBITAL_SCALE);
-            const float y = fmaf(d, cos_rev(ub - (odd ? 0.25f : 0.f)), x(k));
-            return wrap01(large ? (odd ? ub : ua) : y);
-        }
-        if (type == 2) {
-            // orbital second stage (the reverse mode belongs to Green and never gets here): the pair once, the
-            // large-step case (timidAfterLarge) as a select on an unconditional read
-            float z0, z1;
-            orbital_pair(k & ~1u, true, z0, z1);
-            const float zl = s2(k);
-            return wrap01(large ? zl : ((k & 1u) ? z1 : z0));
-        }
-        // iid kernels (Green, Mira): all three modes from unconditional reads and selects
-        const float xk = x(k), a = u1(k), g = s2(k);
-        const float y = large ? a : xk + kelemen_sample(a, KELEMEN_S2);
-        const float z = large ? g : xk + g;
-        const float v = mode == SM_STAGE1 ? y : (mode == SM_STAGE2 ? z : z - (y - xk)); // reverse: y* = z - (y - x)
-        return wrap01(v);
-    }
-    // Orbital pair (k0, k0 + 1), both components of the first- or second-stage proposal at once (accept(): the
-    // per-component form above evaluates the shared radius / angle / rotation twice per pair). Same arithmetic.
-    DEV void orbital_pair(uint32_t k0, bool second, float &o0, float &o1) const {
-        FP_STRICT;
-        const float x0 = x(k0), x1 = x(k0 + 1u);
-        const float d = kelemen_sample(u1(k0), KELEMEN_S2 * ORBITAL_SCALE), a = u1(k0 + 1u);
-        const float y0 = fmaf(d, cos_rev(a), x0), y1 = fmaf(d, cos_rev(a - 0.25f), x1);
-        if (!second) { o0 = y0; o1 = y1; return; }
-        float xi = s2(k0 >> 1);
-        float sign = 1.f;
-        if (xi < 0.5f) { xi *= 2.f; } else { sign = -1.f; xi = 2.f * (xi - 0.5f); }
-        const float V = cos_rev(xi);
-        const float A = fminf(1.f, fmaxf(-1.f, (V + WC_DISPERSION) / (1.f + WC_DISPERSION * V)));
-        const float ct = A, st = sign * sqrtf(fmaxf(0.f, 1.f - A * A));
-        const float dx0 = x0 - y0, dx1 = x1 - y1;
-        o0 = y0 + (ct * dx0 - st * dx1);
-        o1 = y1 + (st * dx0 + ct * dx1);
-    }
-};
-
-// ------------------------------------------------------------------ PSS sampler of k_mutate_v4
-// The proposals themselves are parked in LDS, not the uniforms they are made of: the bookkeeping branch of k_mutate_v4
-// evaluates the transition kernels for ALL dimensions of the chains that start an evaluation, flattened over the 64
-// lanes of the wave (items = chain x Philox block, every lane busy), so that inside the divergent path step a PSS
-// component is one LDS read and a reflection. Three row groups of D4 rows each (stride `stride` floats, column = chain),
-// all three UNWRAPPED; which group plays which role is the chain's own business:
-//   x   current state (wrapped where it is read)
-//   y   first-stage proposal (a large step: the uniforms themselves)
-//   z   second-stage proposal
-// A chain adopts a proposal by exchanging the roles of two of its groups (DRMLTSampler::accept without the copy): x_off and y_off
-// are PER LANE, the float offset of row 0 of the group with the chain's column folded in, each below 2^14 (64 KB of LDS); the z
-// group is the third one (the three offsets add up to `xyz`). Between loop sections a chain keeps the pair in one word (roles()).
-// Same arithmetic per component as LdsSampler (and Sampler): the chains are bit-identical.
-// RULE (device_types.h): under RULE_ORBITAL `type` is 2 at compile time -- the fill routines keep their orbital arm, and `mode` is
-// SM_STAGE1 or SM_STAGE2 (the reverse move is Green's), so a component is ONE read, of y or of z.
-template <int RULE = RULE_GENERIC> struct RowSamplerT {
-    static constexpr bool orbital = RULE == RULE_ORBITAL;
-    static constexpr bool batch_draws = true; // path_step: the (up to) five components of a step are read together, ahead of the hit's digestion
-    uint32_t key0, key1;
-    int mode, type;
-    float sigma2;
-    uint32_t stride, x_off, y_off, xyz;
-
-    DEV void reset_caches() {}
-    DEV float x(uint32_t k) const { return wrap01(lds_x[x_off + k * stride]); }
-    DEV float y_raw(uint32_t k) const { return lds_x[y_off + k * stride]; }
-    DEV uint32_t z_off() const { return xyz - x_off - y_off; }
-    DEV float z_raw(uint32_t k) const { return lds_x[z_off() + k * stride]; }
-    DEV float next(uint32_t k) const {
-        FP_STRICT;
-        if constexpr (orbital) return wrap01(lds_x[(mode == SM_STAGE1 ? y_off : z_off()) + k * stride]);
-        float v = y_raw(k);
-        if (mode != SM_STAGE1) {
-            const float z = z_raw(k);
-            v = mode == SM_STAGE2 ? z : z - (v - x(k)); // Green's reverse move: y* = z - (y - x)
-        }
-        return wrap01(v);
-    }
-    // adopt the first- (SM_STAGE1) or second-stage (SM_STAGE2) proposal: its group becomes x, the old x group is free for the
-    // next proposal of that stage (0: nothing adopted)
-    DEV void adopt(int commit_mode) {
-        const uint32_t xo = x_off, zo = z_off();
-        x_off = commit_mode == SM_STAGE1 ? y_off : (commit_mode == SM_STAGE2 ? zo : xo);
-        y_off = commit_mode == SM_STAGE1 ? xo : y_off;
-    }
-    // The two offsets in one word: what a chain lane keeps across loop sections, and what travels to the lanes that fill ANOTHER
-    // chain's rows in the flattened passes (bit 0 is free for the large-step bit there). `col`: the chain's column.
-    DEV uint32_t roles() const { return (x_off << 1) | (y_off << 16); }
-    DEV void set_roles(uint32_t w, uint32_t group, uint32_t col) { x_off = (w >> 1) & 0x7fffu; y_off = w >> 16; xyz = 3u * (group + col); }
-    DEV static uint32_t first_roles(uint32_t group, uint32_t col) { return (col << 1) | ((group + col) << 16); }
-    // first-stage proposal of the chain whose offsets this sampler carries, dimensions 4b .. 4b+3, from Philox block b of (major, chain)
-    DEV void fill_first(uint32_t b, uint32_t major, uint32_t chain, bool large) const {
-        FP_STRICT;
-        const u4 r = philox4x32_10(key0, key1, b, major, chain, TAG_S1);
-        const float u0 = u32_to_unit(r.x), u1 = u32_to_unit(r.y), u2 = u32_to_unit(r.z), u3 = u32_to_unit(r.w);
-        const float *xs = &lds_x[x_off + 4u * b * stride];
-        float *ys = &lds_x[y_off + 4u * b * stride];
-        const float x0 = wrap01(xs[0]), x1 = wrap01(xs[stride]), x2 = wrap01(xs[2u * stride]), x3 = wrap01(xs[3u * stride]);
-        float y0, y1, y2, y3;
-        if (orbital || type == 2) { // pairwise orbital: radius from the Kelemen kernel (x 1.9), uniform angle (drmlt_sampler.cpp:354-361)
-            const float d0 = kelemen_sample(u0, KELEMEN_S2 * ORBITAL_SCALE), d1 = kelemen_sample(u2, KELEMEN_S2 * ORBITAL_SCALE);
-            y0 = fmaf(d0, cos_rev(u1), x0); y1 = fmaf(d0, cos_rev(u1 - 0.25f), x1);
-            y2 = fmaf(d1, cos_rev(u3), x2); y3 = fmaf(d1, cos_rev(u3 - 0.25f), x3);
-        } else {
-            y0 = x0 + kelemen_sample(u0, KELEMEN_S2); y1 = x1 + kelemen_sample(u1, KELEMEN_S2);
-            y2 = x2 + kelemen_sample(u2, KELEMEN_S2); y3 = x3 + kelemen_sample(u3, KELEMEN_S2);
-        }
-        ys[0] = large ? u0 : y0; ys[stride] = large ? u1 : y1; ys[2u * stride] = large ? u2 : y2; ys[3u * stride] = large ? u3 : y3;
-    }
-    // second-stage proposal of that chain from Philox block b of the TAG_S2 stream: a large step (timidAfterLarge)
-    // -> dims 4b..4b+3 (uniforms); orbital -> the angles of pairs 4b..4b+3 = dims 8b..8b+7; iid kernels -> the Gaussian
-    // perturbations of dims 2b, 2b+1 (draws 2k, 2k+1 belong to dim k). Blocks beyond the chain's kind of stage do nothing.
-    DEV void fill_second(uint32_t b, uint32_t D4, uint32_t major, uint32_t chain, bool large) const {
-        FP_STRICT;
-        const uint32_t nblk = large ? D4 / 4u : ((orbital || type == 2) ? (D4 / 2u + 3u) / 4u : D4 / 2u);
-        if (b >= nblk) return;
-        const u4 r = philox4x32_10(key0, key1, b, major, chain, TAG_S2);
-        const float u[4] = {u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)};
-        const uint32_t zo = z_off();
-        if (large) {
-#pragma unroll
-            for (uint32_t i = 0; i < 4u; ++i) lds_x[zo + (4u * b + i) * stride] = u[i];
-        } else if (orbital || type == 2) {
-            // (all reads first: the writes below are to LDS too and may alias them for the compiler -- pair after pair would wait for its
-            // own reads behind the previous pair's writes)
-            float xa[4], xb[4], ya[4], yb[4];
-#pragma unroll
-            for (uint32_t i = 0; i < 4u; ++i) {
-                const uint32_t k0 = 2u * (4u * b + i), kk = k0 + 1u < D4 ? k0 : 0u;
-                xa[i] = x(kk); xb[i] = x(kk + 1u);
-                ya[i] = y_raw(kk); yb[i] = y_raw(kk + 1u);
-            }
-#pragma unroll
-            for (uint32_t i = 0; i < 4u; ++i) {
-                const uint32_t k0 = 2u * (4u * b + i);
-                if (k0 + 1u < D4) {
-                    const float x0 = xa[i], x1 = xb[i], y0 = ya[i], y1 = yb[i];
-                    // theta ~ wrapped Cauchy by inverse CDF (transition.h:157-173); z = y + R(theta)(x - y) (drmlt_sampler.cpp:374-391)
-                    float xi = u[i], sign = 1.f;
-                    if (xi < 0.5f) { xi *= 2.f; } else { sign = -1.f; xi = 2.f * (xi - 0.5f); }
-                    const float V = cos_rev(xi);
-                    const float A = fminf(1.f, fmaxf(-1.f, (V + WC_DISPERSION) / (1.f + WC_DISPERSION * V)));
-                    const float ct = A, st = sign * sqrtf(fmaxf(0.f, 1.f - A * A));
-                    const float dx0 = x0 - y0, dx1 = x1 - y1;
-                    lds_x[zo + k0 * stride] = y0 + (ct * dx0 - st * dx1);
-                    lds_x[zo + (k0 + 1u) * stride] = y1 + (st * dx0 + ct * dx1);
-                }
-            }
-        } else {
-            const uint32_t k = 2u * b;
-            const float x0 = x(k), x1 = x(k + 1u);
-            lds_x[zo + k * stride] = x0 + gaussian_sample(u[0], u[1], sigma2);
-            lds_x[zo + (k + 1u) * stride] = x1 + gaussian_sample(u[2], u[3], sigma2);
-        }
-    }
-};
-typedef RowSamplerT<> RowSampler;
 
 // ------------------------------------------------------------------ ray queries
 struct Hit {
@@ -443,7 +39,6 @@ template <class T> DEV T load_global16(const T *p) {
 // trips through the L2). The lazy samplers (Philox inside next()) keep the loop: one copy of their code.
 template <class S, class = void> struct draws_batched : std::false_type {};
 template <class S> struct draws_batched<S, std::void_t<decltype(S::batch_draws)>> : std::integral_constant<bool, S::batch_draws> {};
-DEV float load_global_f32(const float *p) { return *(const float __attribute__((address_space(1))) *) (uintptr_t) p; }
 DEV void atomic_add_global_f32(float *p, float v) { // no-return float add on device memory (global_atomic_add_f32)
     (void) __hip_atomic_fetch_add((float __attribute__((address_space(1))) *) (uintptr_t) p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1654,45 +1249,6 @@ DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, Sa
         ps.has_bounce = true;
     }
 }
-
-// PSSMLTSampler (src/integrators/pssmlt/pssmlt_sampler.cpp:93-168, pssmlt_sampler.h:113-143) as a pure function of the
-// addressed stream: at the first primarySample of a mutation the reference rewrites the whole vector in order --
-// components that already exist are mutated (Kelemen: one draw, toroidal wrap; Gaussian: two draws, modulo 1) or
-// redrawn (large step: one draw), components that do not exist yet (beyond what the seed path consumed; only possible
-// in a chain's first mutation) are appended as fresh uniforms (one draw) and survive a rejection.
-struct PssmltSampler {
-    uint32_t key0, key1, chain, major;
-    bool large, kelemen;
-    float sigma;
-    uint32_t lane;
-    uint32_t n_exist; // components that exist before this mutation
-    u4 b1;
-    uint32_t b1_idx;
-    DEV void reset_caches() { b1_idx = 0xffffffffu; }
-    DEV float u_s1(uint32_t idx) {
-        uint32_t blk = idx >> 2;
-        if (blk != b1_idx) { b1 = philox4x32_10(key0, key1, blk, major, chain, TAG_S1); b1_idx = blk; }
-        return pick4(b1, idx & 3u);
-    }
-    DEV float x(uint32_t k) const { return lds_x[k * 64u + lane]; }
-    DEV float next(uint32_t k) {
-        const uint32_t per = (large || kelemen) ? 1u : 2u; // draws taken by an existing component
-        if (k >= n_exist) return u_s1(per * n_exist + (k - n_exist));
-        if (large) return u_s1(k);
-        float value = x(k);
-        if (kelemen) {
-            float xi = u_s1(k);
-            const bool add = xi < 0.5f;
-            xi = add ? 2.f * xi : 2.f * (xi - 0.5f);
-            const float dv = KELEMEN_S2 * fast_exp2(xi * LOG2_S1_OVER_S2);
-            if (add) { value += dv; if (value > 1.f) value -= 1.f; }
-            else { value -= dv; if (value < 0.f) value += 1.f; }
-            return value;
-        }
-        const float v = value + gaussian_sample(u_s1(2u * k), u_s1(2u * k + 1u), sigma);
-        return v - floorf(v); // math::modulo(v, 1)
-    }
-};
 
 // Run one full PSS evaluation (one wave-divergent loop; every step issues at most one ray query).
 template <class SamplerT> DEV DSplat eval_path(const DParams &P, SamplerT &smp, uint32_t &nrays, uint32_t &ndims) {

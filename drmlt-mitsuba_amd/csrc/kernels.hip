@@ -23,7 +23,7 @@
 __device__ __attribute__((noinline)) DSplat eval_boot_sample(const DParams &P, uint32_t index, uint32_t &nd) {
     Sampler smp;
     smp.key0 = P.key0; smp.key1 = P.key1; smp.chain = P.boot_stream; smp.major = index;
-    smp.mode = SM_BOOT; smp.type = P.type; smp.large = false; smp.sigma2 = P.sigma2; smp.lane = 0u; smp.arr = nullptr;
+    smp.mode = SM_BOOT; smp.arr = nullptr;
     uint32_t nr;
     return eval_path(P, smp, nr, nd);
 }
@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(64) k_init_chains(DParams P, const uint32_t *s
     if (c >= P.n_chains) return;
     Sampler smp;
     smp.key0 = P.key0; smp.key1 = P.key1; smp.chain = P.boot_stream; smp.major = seed_index[c];
-    smp.mode = SM_BOOT; smp.type = P.type; smp.large = false; smp.sigma2 = P.sigma2; smp.lane = 0u; smp.arr = nullptr;
+    smp.mode = SM_BOOT; smp.arr = nullptr;
     uint32_t nd;
     DSplat s = eval_boot_sample(P, smp.major, nd);
     // sanity check of drmlt_proc.cpp:509-512: same function, same inputs -> bit-equal on the device
@@ -250,12 +250,11 @@ DEV int mh_start(const DParams &P, ChainState &cs, LdsSampler &smp, PathState &p
 // ------------------------------------------------------------------------------------------
 // k_mutate_v3: two lanes per chain. 64 k chains are only 1024 waves = ONE wave per SIMD: every
 // LDS / scalar-cache / transcendental latency is exposed and a lone wave can issue a VALU op only
-// every 4 cycles (MI355X_MICROARCH.md). Lanes 0..31 of a wave run the chain state machines of
-// k_mutate_v2; lane 32+i is the helper of lane i and traces the shadow (NEE) ray of a vertex
+// every 4 cycles (MI355X_MICROARCH.md). Lanes 0..31 of a wave run the chain state machines;
+// lane 32+i is the helper of lane i and traces the shadow (NEE) ray of a vertex
 // while lane i traces the BSDF-sampled ray of the same vertex. A bounce then costs one loop
 // iteration instead of two, a wave carries 32 chains, and the same 64 k chains occupy 2048
-// waves = two per SIMD, which hide each other's latencies. Per chain the arithmetic and the
-// order of all additions are those of k_mutate_v2.
+// waves = two per SIMD, which hide each other's latencies.
 DEV float from_lower(float v) { // value of lane (l & 31) for every lane l (v_permlane32_swap)
     unsigned u = __float_as_uint(v);
     return __uint_as_float(__builtin_amdgcn_permlane32_swap(u, u, false, false)[0]);
@@ -294,7 +293,6 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v3(DParams P, uint32_t n
     smp.stride = 32u;
     smp.u1_off = (uint32_t) D * 32u;
     smp.s2_off = smp.u1_off + D4 * 32u;
-    smp.timing_probe = false;
     Counters ct = {0u, 0u, 0u, 0u, 0u};
     PathState ps;
     path_init(P, ps);
@@ -438,7 +436,7 @@ DEV int mh_resolve_kind(const DParams &Pm, int kind, bool live, uint32_t done_no
 // reference's own PSSMLT loop does the same (pssmlt_proc.cpp:215-226,262-266); splatting is linear, the film is the
 // same sum. An accepted proposal's weight starts the cumulative weight of the new current state.
 //
-// Chains are the same as k_mutate_v2/v3's (same addressed draws, same arithmetic per chain).
+// Chains are the same as k_mutate_v3's (same addressed draws, and the one copy of the arithmetic: device_sampler.h).
 // (V4_STRIDE, V4_QCAP, V4_QCAP_BVH: launch_plan.h)
 #define V4_STACK32_CAP 11 // LDS entries of a 32-bit traversal stack (the rest spills): 11 + 3 spare rows of 256 B keep eight waves on a CU
 
@@ -899,7 +897,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
 // mutation, L2 / MALL resident). LDS holds ONE row group: the proposal under evaluation -- y, overwritten in place by z when a
 // chain enters its second stage. The orbital rule needs only the luminances of y afterwards; Green's reverse move and Mira's
 // ratio need x, y and z together and RECOMPUTE what the rows no longer hold from the state and the addressed stream (Green:
-// v5_iid_second_again, flattened; Mira: PoolRowSampler::y_raw, per deciding lane -- a twentieth of the mutations get that far).
+// v5_iid_second_again, flattened; Mira: PoolRowSampler::y_raw, per deciding lane -- a twentieth of the mutations get that far;
+// the rows, the sampler and the fill routines: device_sampler.h).
 // Bookkeeping is v4's: decide per lane, commit / proposals / coins flattened over the 64 lanes. Same addressed draws, same arithmetic per component: the same chains.
 // (V5_QCAP, V5_QCAP_STACK32, V5_SLOTS, v5_lds_bytes: launch_plan.h)
 #define V5_STACK32_CAP 25 // (no splat queue, coins drawn per lane instead of kept in four rows: 28 rows of 256 B for the column; measured on 50 000 /
@@ -928,167 +927,6 @@ DEV V5Lds v5_layout(uint32_t D, uint32_t qcap, bool coin_rows) {
     L.ring_off = L.pool_off + 8u * V5_SLOTS;
     L.status_off = L.ring_off + V5_SLOTS / 4u;
     return L;
-}
-
-// Where a wave's proposal rows live. RowsLds: 64 columns of lds_x (one per chain of the wave). RowsMem: device memory, [dim][chain]
-// beside the state -- the builds that give the rows' 8.7 KB of LDS (and a few registers) for a THIRD wave per SIMD on scenes that
-// are traversed: there the wave is parked on node fetches more than half of its time, and what covers a fetch is another wave
-// (1 -> 2 waves per SIMD: x 1.69 on 1 000 000 triangles, x 1.58 on 50 000). A path step reads its handful of components
-// through the L2s instead of LDS: one more fetch beside the ~60 node fetches of the ray it follows.
-struct RowsLds {
-    DEV float get(uint32_t k, uint32_t col) const { return lds_x[k * 64u + col]; }
-    DEV void put(uint32_t k, uint32_t col, float v) const { lds_x[k * 64u + col] = v; }
-};
-struct RowsMem {
-    typedef float __attribute__((address_space(1))) *GPtr;
-    GPtr base;       // column 0 of this wave: P.rows + wave_base
-    uint32_t stride; // P.n_chains
-    // (plain loads and stores: with the streaming hint -- nt, to keep the L2 lines for the BVH -- the row reads themselves miss:
-    // 50 000 triangles 3.13e8 -> 2.79e8, 1 000 000 9.16e7 -> 8.52e7. The same hint on the STATE instead -- read once per mutation,
-    // a whole mutation of every wave of the XCD apart: it does not survive in the L2 anyway -- loses as well: Cornell at 196 608
-    // chains 2.54e9 -> 2.18e9, door 1.09e9 -> 1.05e9, 50 000 triangles 3.45e8 -> 3.26e8. nt bypasses more than the L2.)
-    DEV float get(uint32_t k, uint32_t col) const { return base[(size_t) k * stride + col]; }
-    DEV void put(uint32_t k, uint32_t col, float v) const { base[(size_t) k * stride + col] = v; }
-};
-
-// the proposal rows as the path step sees them: whatever stage is being evaluated sits in the one row group
-template <class Rows> struct PoolRowSampler {
-    static constexpr bool batch_draws = true; // (device_path.h: path_step reads a step's components together)
-    uint32_t lane;
-    Rows rows;
-    // Mira's ratio alone looks behind the rows (they hold z by then): the state in device memory and the first-stage draws,
-    // set by the kernel before a decision (mira_*), block cache of the TAG_S1 stream
-    const float *mira_x = nullptr;
-    size_t mira_stride = 0;
-    uint32_t mira_k0 = 0u, mira_k1 = 0u, mira_major = 0u, mira_chain = 0u, cached = 0xffffffffu;
-    u4 blk = {0u, 0u, 0u, 0u};
-    DEV void reset_caches() { cached = 0xffffffffu; }
-    DEV float row(uint32_t k) const { return rows.get(k, lane); }
-    DEV float next(uint32_t k) const { return wrap01(row(k)); }
-    DEV float x(uint32_t k) const { return load_global_f32(mira_x + (size_t) k * mira_stride); }
-    DEV float y_raw(uint32_t k) { // iid Kelemen step, small (the only caller: mira_ratio)
-        FP_STRICT;
-        if (cached != (k >> 2)) { cached = k >> 2; blk = philox4x32_10(mira_k0, mira_k1, cached, mira_major, mira_chain, TAG_S1); }
-        // (values, not loads: a select between two single-use loads of this struct's fields becomes a load through a selected
-        // ADDRESS and the whole sampler -- 60 bytes per lane -- then lives in scratch memory: VERDICT r03 #8)
-        uint32_t bx = blk.x, by = blk.y, bz = blk.z, bw = blk.w;
-        asm volatile("" : "+v"(bx), "+v"(by), "+v"(bz), "+v"(bw));
-        const uint32_t c = k & 3u, w = (c & 2u) ? ((c & 1u) ? bw : bz) : ((c & 1u) ? by : bx);
-        return x(k) + kelemen_sample(u32_to_unit(w), KELEMEN_S2);
-    }
-    DEV float z_raw(uint32_t k) const { return row(k); }
-};
-
-// first-stage proposal of the chain in column `col` (state column `xcol` of P.x), dimensions 4b .. 4b+3, from Philox block b
-// (the four state components of the block are read by the CALLER, one pass of the flattened loop ahead: v5_state4)
-struct State4 { float x0, x1, x2, x3; };
-DEV State4 v5_state4(const DParams &P, uint32_t D, size_t xcol, uint32_t b) {
-    const bool hi = 4u * b + 2u < D; // D is even: a block holds two pairs or, at the end of the vector, one
-    const float *xs = P.x + (size_t) (4u * b) * P.n_chains + xcol;
-    State4 X;
-    X.x0 = load_global_f32(xs); X.x1 = load_global_f32(xs + P.n_chains);
-    X.x2 = load_global_f32(xs + (hi ? 2u : 0u) * (size_t) P.n_chains); X.x3 = load_global_f32(xs + (hi ? 3u : 1u) * (size_t) P.n_chains);
-    return X;
-}
-template <class Rows> DEV void v5_fill_first(const DParams &P, const Rows &rows, uint32_t D, uint32_t col, const State4 &X, uint32_t b, uint32_t major, uint32_t chain, bool large) {
-    FP_STRICT;
-    const u4 r = philox4x32_10(P.key0, P.key1, b, major, chain, TAG_S1);
-    const float u0 = u32_to_unit(r.x), u1 = u32_to_unit(r.y), u2 = u32_to_unit(r.z), u3 = u32_to_unit(r.w);
-    const bool hi = 4u * b + 2u < D;
-    const float x0 = X.x0, x1 = X.x1, x2 = X.x2, x3 = X.x3;
-    float y0, y1, y2, y3;
-    if (P.type == 2) { // pairwise orbital: radius from the Kelemen kernel (x 1.9), uniform angle (drmlt_sampler.cpp:354-361)
-        const float d0 = kelemen_sample(u0, KELEMEN_S2 * ORBITAL_SCALE), d1 = kelemen_sample(u2, KELEMEN_S2 * ORBITAL_SCALE);
-        y0 = fmaf(d0, cos_rev(u1), x0); y1 = fmaf(d0, cos_rev(u1 - 0.25f), x1);
-        y2 = fmaf(d1, cos_rev(u3), x2); y3 = fmaf(d1, cos_rev(u3 - 0.25f), x3);
-    } else { // iid Kelemen kernel (Green, Mira)
-        y0 = x0 + kelemen_sample(u0, KELEMEN_S2); y1 = x1 + kelemen_sample(u1, KELEMEN_S2);
-        y2 = x2 + kelemen_sample(u2, KELEMEN_S2); y3 = x3 + kelemen_sample(u3, KELEMEN_S2);
-    }
-    rows.put(4u * b, col, large ? u0 : y0); rows.put(4u * b + 1u, col, large ? u1 : y1);
-    if (hi) { rows.put(4u * b + 2u, col, large ? u2 : y2); rows.put(4u * b + 3u, col, large ? u3 : y3); }
-}
-// second-stage proposal from Philox block b of the TAG_S2 stream, written OVER the first-stage rows: a large step
-// (timidAfterLarge) -> dims 4b .. 4b+3 (uniforms); orbital -> the angles of pairs 4b .. 4b+3 = dims 8b .. 8b+7 (reads the y rows
-// it replaces); iid kernels -> the Gaussian perturbations of dims 2b, 2b+1 (draws 2k, 2k+1 belong to dim k)
-template <class Rows> DEV void v5_fill_second(const DParams &P, const Rows &rows, uint32_t D, uint32_t col, size_t xcol, uint32_t b, uint32_t major, uint32_t chain, bool large) {
-    FP_STRICT;
-    const u4 r = philox4x32_10(P.key0, P.key1, b, major, chain, TAG_S2);
-    const float u[4] = {u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)};
-    if (large) {
-#pragma unroll
-        for (uint32_t i = 0; i < 4u; ++i)
-            if (4u * b + i < D) rows.put(4u * b + i, col, u[i]);
-        return;
-    }
-    if (P.type != 2) {
-        const uint32_t k = 2u * b; // (k + 1 < D: the caller's block count)
-        const float x0 = load_global_f32(P.x + (size_t) k * P.n_chains + xcol), x1 = load_global_f32(P.x + (size_t) (k + 1u) * P.n_chains + xcol);
-        rows.put(k, col, x0 + gaussian_sample(u[0], u[1], P.sigma2));
-        rows.put(k + 1u, col, x1 + gaussian_sample(u[2], u[3], P.sigma2));
-        return;
-    }
-    // (all loads first: the stores below may alias them for the compiler, and with the rows in device memory every pair would
-    // otherwise wait for its own round trip behind the previous pair's stores)
-    float xa[4], xb[4], ya[4], yb[4];
-#pragma unroll
-    for (uint32_t i = 0; i < 4u; ++i) {
-        const uint32_t k0 = 2u * (4u * b + i);
-        const uint32_t kk = k0 + 1u < D ? k0 : 0u;
-        xa[i] = load_global_f32(P.x + (size_t) kk * P.n_chains + xcol); xb[i] = load_global_f32(P.x + (size_t) (kk + 1u) * P.n_chains + xcol);
-        ya[i] = rows.get(kk, col); yb[i] = rows.get(kk + 1u, col);
-    }
-#pragma unroll
-    for (uint32_t i = 0; i < 4u; ++i) {
-        const uint32_t k0 = 2u * (4u * b + i);
-        if (k0 + 1u < D) {
-            const float x0 = xa[i], x1 = xb[i], y0 = ya[i], y1 = yb[i];
-            // theta ~ wrapped Cauchy by inverse CDF (transition.h:157-173); z = y + R(theta)(x - y) (drmlt_sampler.cpp:374-391)
-            float xi = u[i], sign = 1.f;
-            if (xi < 0.5f) { xi *= 2.f; } else { sign = -1.f; xi = 2.f * (xi - 0.5f); }
-            const float V = cos_rev(xi);
-            const float A = fminf(1.f, fmaxf(-1.f, (V + WC_DISPERSION) / (1.f + WC_DISPERSION * V)));
-            const float ct = A, st = sign * sqrtf(fmaxf(0.f, 1.f - A * A));
-            const float dx0 = x0 - y0, dx1 = x1 - y1;
-            rows.put(k0, col, y0 + (ct * dx0 - st * dx1));
-            rows.put(k0 + 1u, col, y1 + (st * dx0 + ct * dx1));
-        }
-    }
-}
-// Green & Mira's reverse move and the adoption of a second-stage proposal under Green, for the iid kernels: dims 2b, 2b+1
-// from Philox block b of TAG_S2 (z = x + g), block b / 2 of TAG_S1 (y = x + kelemen) and the state in device memory.
-//   reverse:  rows := y* = z - (y - x)   (drmlt_proc.cpp:588-598; the rows held z, which is recomputed, not read)
-//   !reverse: state := wrap(z)            (the rows hold y* by then: DRMLTSampler::accept(second), drmlt_sampler.cpp:189-199)
-// A large step (timidAfterLarge): y and z are the uniforms themselves, dims 4b .. 4b+3 of block b of either stream.
-template <class Rows> DEV void v5_iid_second_again(const DParams &P, const Rows &rows, uint32_t D, uint32_t col, size_t xcol, uint32_t b, uint32_t major, uint32_t chain, bool large, bool reverse) {
-    FP_STRICT;
-    const u4 r2 = philox4x32_10(P.key0, P.key1, b, major, chain, TAG_S2);
-    const float u2[4] = {u32_to_unit(r2.x), u32_to_unit(r2.y), u32_to_unit(r2.z), u32_to_unit(r2.w)};
-    if (large) {
-        u4 r1 = r2;
-        if (reverse) r1 = philox4x32_10(P.key0, P.key1, b, major, chain, TAG_S1);
-        const float u1[4] = {u32_to_unit(r1.x), u32_to_unit(r1.y), u32_to_unit(r1.z), u32_to_unit(r1.w)};
-#pragma unroll
-        for (uint32_t i = 0; i < 4u; ++i) {
-            const uint32_t k = 4u * b + i;
-            if (k < D) {
-                float *xg = P.x + (size_t) k * P.n_chains + xcol;
-                if (reverse) rows.put(k, col, u2[i] - (u1[i] - load_global_f32(xg)));
-                else *xg = wrap01(u2[i]);
-            }
-        }
-        return;
-    }
-    const uint32_t k = 2u * b;
-    float *xg0 = P.x + (size_t) k * P.n_chains + xcol, *xg1 = xg0 + P.n_chains;
-    const float x0 = load_global_f32(xg0), x1 = load_global_f32(xg1);
-    const float z0 = x0 + gaussian_sample(u2[0], u2[1], P.sigma2), z1 = x1 + gaussian_sample(u2[2], u2[3], P.sigma2);
-    if (!reverse) { *xg0 = wrap01(z0); *xg1 = wrap01(z1); return; }
-    const u4 r1 = philox4x32_10(P.key0, P.key1, k >> 2, major, chain, TAG_S1);
-    const float ua = (k & 2u) ? u32_to_unit(r1.z) : u32_to_unit(r1.x), ub = (k & 2u) ? u32_to_unit(r1.w) : u32_to_unit(r1.y);
-    const float y0 = x0 + kelemen_sample(ua, KELEMEN_S2), y1 = x1 + kelemen_sample(ub, KELEMEN_S2);
-    rows.put(k, col, z0 - (y0 - x0));
-    rows.put(k + 1u, col, z1 - (y1 - x1));
 }
 
 // FEAT & 8 (BVH scenes): the traversal loop described above. Flat scenes (FEAT without bit 3; LDS_TABLES: their shading /
@@ -1563,7 +1401,7 @@ __global__ void __launch_bounds__(64) k_eval_paths(DParams P, const float *u, ui
     if (i >= n) return;
     Sampler smp;
     smp.key0 = smp.key1 = smp.chain = smp.major = 0u;
-    smp.mode = SM_ARRAY; smp.type = P.type; smp.large = false; smp.sigma2 = P.sigma2; smp.lane = 0u;
+    smp.mode = SM_ARRAY;
     smp.arr = u + (size_t) i * dim;
     uint32_t nr, nd;
     DSplat s = eval_path(P, smp, nr, nd);
@@ -1578,7 +1416,7 @@ __global__ void __launch_bounds__(64) k_render_pt(DParams P, uint64_t n_samples,
     for (; i < n_samples; i += stride) {
         Sampler smp;
         smp.key0 = P.key0; smp.key1 = P.key1; smp.chain = stream + (uint32_t) (i >> 32); smp.major = (uint32_t) i;
-        smp.mode = SM_PT; smp.type = P.type; smp.large = false; smp.sigma2 = P.sigma2; smp.lane = 0u; smp.arr = nullptr;
+        smp.mode = SM_PT; smp.arr = nullptr;
         uint32_t nr, nd;
         DSplat s = eval_path(P, smp, nr, nd);
         if (s.lum > 0.f) film_put(P, s.px, s.py, mk3(s.r * scale, s.g * scale, s.b * scale));

@@ -1,4 +1,4 @@
-"""k_mutate_v4 adopts a proposal by exchanging the roles of two of the chain's LDS row groups (RowSampler, device_path.h): no
+"""k_mutate_v4 adopts a proposal by exchanging the roles of two of the chain's LDS row groups (RowSampler, device_sampler.h): no
 commit pass, the current state is kept unwrapped and wrapped where it is read. The chains must stay those of k_mutate_v3, which
 commits with an explicit wrapped copy -- bit for bit: states, f(u) of the current state, mutation and acceptance counts."""
 import os
