@@ -630,6 +630,22 @@ struct LdsTables {
     }
     DEV float emitter_cdf_lo(int i) const { return lds_x[emit_off + (uint32_t) i * 8u + 4u]; }
     DEV DShade emitter_shade(int, const DEmitter &E) const { return shade(E.prim); }
+    DEV int n_emitters(const DParams &P) const { return P.n_emitters; } // bound of path_step_diffuse's light pick
+};
+// LdsTables for a scene with one light (device_types.h: scene_has_one_light): every emitter index is 0, so the emitter's record and
+// its shape's are the parameter block's joined copy -- wave-uniform scalars of the section's own block, loaded on the wait the
+// section pays anyway -- and the light pick is an empty loop at compile time. The hit's shading record and the BSDFs stay in LDS.
+struct OneLightTables {
+    LdsTables L;
+    const DParams &P;
+    DEV DShade shade(int i) const { return L.shade(i); }
+    DEV DBsdf bsdf(int i) const { return L.bsdf(i); }
+    DEV DEmitter emitter(int) const { return P.light; }
+    DEV float emitter_cdf_lo(int) const { return P.light.cdf_lo; }
+    // (inv_area is pinned where the record is asked for: its only use sits in a conditional block, and the compiler would sink the
+    // scalar load into it -- a wait of its own in the middle of the step instead of the one at the section's head)
+    DEV DShade emitter_shade(int, const DEmitter &) const { DShade s = P.light_shade; asm volatile("" : "+s"(s.inv_area)); return s; }
+    DEV constexpr int n_emitters(const DParams &) const { return 1; }
 };
 // BSDF and emitter records in LDS, shading records in device memory: for kernels whose own rows leave less LDS than the shading table
 // needs (k_mutate_bdpt at two waves per SIMD: 19.25 KB of rows; the Cornell scene's 30 shading records are 1.9 KB, its four BSDFs and one
@@ -1192,7 +1208,7 @@ DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, Sa
     const float by = bpos == 0 ? v1 : (bpos == 1 ? v2 : (bpos == 2 ? v3 : v4));
     // direct illumination sampling
     int ei = 0; // DiscreteDistribution::sample (lower_bound semantics); the loop is wave-uniform
-    for (int i = 1; i < P.n_emitters; ++i)
+    for (int i = 1; i < T.n_emitters(P); ++i)
         if (T.emitter_cdf_lo(i) < sx0) ei = i;
     const DEmitter E = T.emitter(ei);
     const float emPdf = E.cdf_hi - E.cdf_lo;

@@ -168,6 +168,10 @@ struct DParams {
     int32_t env_emitter;         // index of the constant environment emitter (read under feature bit 4 only), or -1: a ray that leaves the scene ends the path
     float *rows;                 // k_mutate_v5 with its proposal rows in device memory ([dim][chain], as x), or NULL: rows in LDS
     int32_t boot_weighted;       // bootstrap kernels: also write each sample's luminance under the importance map, to lum_out[n + i] (two-stage MLT: seeds drawn from the chains' own target, drmlt_capi.cpp)
+    // the scene's first light, joined (scene_prep.h, whenever n_emitters >= 1): byte copies of emitters[0] and shade[emitters[0].prim].
+    // A section's own copy of the block delivers them as scalar loads (device_path.h: OneLightTables; scene_has_one_light below)
+    DEmitter light;
+    DShade light_shade;
 };
 
 // Compile-time rule tag of the chain loop (k_mutate_v4's bodies; mh_digest and RowSampler take it as a template parameter).
@@ -182,6 +186,18 @@ enum { RULE_GENERIC = 0, RULE_ORBITAL = 1 };
 enum { DBG_RULE_GENERIC = 2048 };
 constexpr bool rule_is_orbital(const DParams &P) {
     return P.type == 2 && P.use_mixture == 0 && P.acceptance_map == 0 && (P.debug & DBG_RULE_GENERIC) == 0;
+}
+
+// Compile-time light tag of k_mutate_v4's straight-line step (path_step_diffuse). A scene with ONE emitter picks emitter 0 at every
+// vertex of every path: the one-light builds read its record and its shape's record from the parameter block (P.light, P.light_shade:
+// wave-uniform scalars) where the generic builds fetch them per lane from the staged tables behind the pick.
+// scene_has_one_light is the ONE place the predicate is written down: one emitter, an area emitter on a shape the step samples (a
+// rectangle or a triangle -- a point light's record is tagged PRIM_POINT, the environment's PRIM_ENV, a sphere's PRIM_SPHERE). A
+// context created under DRMLT_ONE_LIGHT_GENERIC carries DBG_ONE_LIGHT_GENERIC in its debug mask and runs the generic build.
+enum { DBG_ONE_LIGHT_GENERIC = 4096 };
+constexpr bool scene_has_one_light(const DParams &P) {
+    return P.n_emitters == 1 && P.light_shade.emitter == 0 &&
+           ((P.light_shade.bsdf >> 24) == PRIM_RECTANGLE || (P.light_shade.bsdf >> 24) == PRIM_TRIANGLE) && (P.debug & DBG_ONE_LIGHT_GENERIC) == 0;
 }
 
 // result of one PSS evaluation, SoA-friendly

@@ -700,7 +700,8 @@ int drmlt_stats_get(drmlt_ctx *ctx, drmlt_stats *o) {
         fprintf(stderr, "[drmlt bvh] wave iterations: inner %llu (%.1f lanes each), leaf %llu (%.1f lanes each)\n", v[12], (double) v[10] / (double) v[12], v[13],
                 v[13] ? (double) v[11] / (double) v[13] : 0.0);
     if (ctx->knobs.verbose && ctx->P.kernel_variant == 4)
-        fprintf(stderr, "[drmlt v4] waves through the orbital rule body: %llu\n", v[14]);
+        fprintf(stderr, "[drmlt v4] waves through the orbital rule body: %llu\n", v[14]),
+        fprintf(stderr, "[drmlt v4] waves through a one-light build: %llu\n", v[15]);
     if ((ctx->P.debug & 1024) && v[20] && ctx->P.kernel_variant != 5)
         fprintf(stderr, "[drmlt bvh] lanes at slice start, of 64: tracing %.1f, chain waiting for its partner %.1f, chain parked for bookkeeping %.1f, helper idle %.1f, flush %.1f (%llu slices)\n",
                 (double) v[21] / v[20], (double) v[22] / v[20], (double) v[23] / v[20], (double) v[24] / v[20], (double) v[25] / v[20], v[20]);

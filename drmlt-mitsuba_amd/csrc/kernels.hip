@@ -528,14 +528,21 @@ template <int RULE> DEV V4Layout<RULE> v4_layout(const DParams &P, uint32_t qcap
 // kernels keep their names and their code. V4_F3_STAMPS, a diagnostic build, has none (its twin spills 54 scalar registers where
 // it spills 52: its stamps are those of the generic build). The BVH builds and the builds with their tables in device memory have no twin: their
 // time is in the traversal and in table fetches. stats[14] counts the waves that ran an orbital build (DRMLT_VERBOSE prints it with drmlt_stats_get).
+// BUILD also carries V4_ONE_LIGHT_BUILD * ONE_LIGHT: V4_F0 and V4_F0_STAMPS, the builds with the straight-line step, have under both
+// rules a twin whose step reads the scene's one light from the parameter block (device_path.h: OneLightTables); launch_mutate selects
+// it by scene_has_one_light(P) (device_types.h), again without a Build enumerator. stats[15] counts the waves that ran a one-light build.
 #define V4_ORBITAL_BUILD 16
+#define V4_ONE_LIGHT_BUILD 32
 template <int BUILD, bool LDS_TABLES, bool STAMPS, bool STACK16 = false, bool OVF = false>
 __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n_mut, uint32_t mut_base) {
-    constexpr int FEAT = BUILD & (V4_ORBITAL_BUILD - 1), RULE = BUILD / V4_ORBITAL_BUILD;
+    constexpr int FEAT = BUILD & (V4_ORBITAL_BUILD - 1), RULE = (BUILD & V4_ORBITAL_BUILD) / V4_ORBITAL_BUILD;
+    constexpr bool ONE_LIGHT = (BUILD & V4_ONE_LIGHT_BUILD) != 0;
+    static_assert(!ONE_LIGHT || (FEAT == 0 && LDS_TABLES), "the one-light twins are those of the straight-line step");
     typedef RowSamplerT<RULE> RowSampler;
     typedef V4Layout<RULE> V4Layout;
     constexpr bool orbital = RULE == RULE_ORBITAL; // stage 2 (Green's reverse move, kind 3, SM_REVERSE) does not occur
     if (orbital && threadIdx.x == 0) atomicAdd(P.stats + 14, 1ull);
+    if (ONE_LIGHT && threadIdx.x == 0) atomicAdd(P.stats + 15, 1ull);
     // The parameter block is ~80 dwords, most of it used by one loop section only. Left to itself the compiler loads every
     // field it will ever need before the loop and then spills scalar registers into vector lanes all through the loop
     // (a sixth of the kernel's VALU instructions were v_readlane / v_writelane). Each loop section therefore works on its
@@ -602,9 +609,15 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
 
     constexpr bool prio = true; // wave priority by loop section (see k_mutate_v3)
     constexpr bool stamps = STAMPS;
-    unsigned long long t_mh = 0, t_trace = 0, t_step = 0, n_iter = 0, n_mh = 0, n_busy = 0;
+    // The stamps builds keep sixteen wave-uniform accumulators in scalar registers across the loop. The one-light twins count their
+    // EVENTS (iterations, branches, tracing lanes, the histogram) in 32 bits per wave and launch -- at most 40 960 mutations per
+    // chain (a slice of 32 768 and the run-ahead cap), some six iterations each, times 64 lanes: far from 2^32 -- so that they
+    // spill no more scalars than the builds they replace; cycle sums stay 64-bit. The other builds keep their code.
+    typedef typename std::conditional<ONE_LIGHT, uint32_t, unsigned long long>::type StampCount;
+    unsigned long long t_mh = 0, t_trace = 0, t_step = 0;
+    StampCount n_iter = 0, n_mh = 0, n_busy = 0;
     unsigned long long t_decide = 0, t_commit = 0, t_start = 0, t_fill = 0;
-    unsigned long long hist[6] = {0, 0, 0, 0, 0, 0};
+    StampCount hist[6] = {0, 0, 0, 0, 0, 0};
     unsigned long long dg[6] = {0, 0, 0, 0, 0, 0};
 #define STAMP() (stamps ? __builtin_amdgcn_s_memtime() : 0ull)
     for (;;) {
@@ -771,7 +784,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
                     const V4Layout Y = v4_layout<RULE>(Ps, QCAP);
                     RowSampler smp = Y.smp;
                     smp.set_roles(roles, Y.group, sub); smp.mode = smp_mode;
-                    if constexpr (FEAT == 0 && LDS_TABLES) path_step_diffuse(Ps, Y.LT, ps, smp, h, occluded == 0u, sr); // diffuse polygons: straight-line step
+                    if constexpr (ONE_LIGHT) path_step_diffuse(Ps, OneLightTables{Y.LT, Ps}, ps, smp, h, occluded == 0u, sr); // ... with the light in scalar registers
+                    else if constexpr (FEAT == 0 && LDS_TABLES) path_step_diffuse(Ps, Y.LT, ps, smp, h, occluded == 0u, sr); // diffuse polygons: straight-line step
                     else if (LDS_TABLES) path_step<true, FEAT, RowSampler, LdsTables, false>(Ps, Y.LT, ps, smp, h, occluded == 0u, sr);
                     else path_step<true, FEAT, RowSampler, GlobalTables, false>(Ps, GlobalTables{Ps.shade, Ps.bsdfs, Ps.emitters}, ps, smp, h, occluded == 0u, sr);
                 }
@@ -847,8 +861,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n
     v4_flush(Pe, Y.L, qn, lane);
     if (stamps && lane == 0) {
         atomicAdd(Pe.stats + 16, t_mh); atomicAdd(Pe.stats + 17, t_trace); atomicAdd(Pe.stats + 18, t_step);
-        atomicAdd(Pe.stats + 19, n_iter); atomicAdd(Pe.stats + 20, n_mh); atomicAdd(Pe.stats + 21, n_busy);
-        for (int q = 0; q < 6; ++q) atomicAdd(Pe.stats + 26 + q, hist[q]);
+        atomicAdd(Pe.stats + 19, (unsigned long long) n_iter); atomicAdd(Pe.stats + 20, (unsigned long long) n_mh); atomicAdd(Pe.stats + 21, (unsigned long long) n_busy);
+        for (int q = 0; q < 6; ++q) atomicAdd(Pe.stats + 26 + q, (unsigned long long) hist[q]);
         atomicAdd(Pe.stats + 22, t_decide); atomicAdd(Pe.stats + 23, t_commit); atomicAdd(Pe.stats + 24, t_start); atomicAdd(Pe.stats + 25, t_fill);
     }
 
@@ -1484,7 +1498,8 @@ void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint
     if (plan.verbose && !plan.note.empty()) fprintf(stderr, "%s\n", plan.note.c_str());
 #define LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(plan.grid), dim3(CHAIN_BLOCK), plan.lds, st, P, n_mut, mut_base); break
 #define LAUNCH_RULE(FEAT, ...) if (orbital) { LAUNCH(k_mutate_v4<FEAT | V4_ORBITAL_BUILD, __VA_ARGS__>); } LAUNCH(k_mutate_v4<FEAT, __VA_ARGS__>)
-    const bool orbital = rule_is_orbital(P);
+#define LAUNCH_LIGHT(...) if (one_light) { LAUNCH_RULE(V4_ONE_LIGHT_BUILD, __VA_ARGS__); } LAUNCH_RULE(0, __VA_ARGS__)
+    const bool orbital = rule_is_orbital(P), one_light = scene_has_one_light(P);
     switch (plan.build) {
     case Build::PSSMLT: LAUNCH(k_mutate_pssmlt);
     // k_mutate_v5 <FEAT, STACK16, OVF, STAMPS, LDS_TABLES, ROWS_MEM>: ray pool, 64 chains per wave
@@ -1500,8 +1515,9 @@ void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint
     case Build::V5_F8_OVF: LAUNCH(k_mutate_v5<8, true, true>);  case Build::V5_F15_OVF: LAUNCH(k_mutate_v5<15, true, true>);
     case Build::V5_F8_STAMPS: LAUNCH(k_mutate_v5<8, true, false, true>); case Build::V5_F8: LAUNCH(k_mutate_v5<8, true, false>); case Build::V5_F15: LAUNCH(k_mutate_v5<15, true, false>);
     // k_mutate_v4 <FEAT, LDS_TABLES, STAMPS, STACK16, OVF>: lane pairs, 32 chains per wave
-    // (LAUNCH_RULE: the orbital twin of the build when the context's rule is the orbital one)
-    case Build::V4_F0_STAMPS: LAUNCH_RULE(0, true, true); case Build::V4_F0: LAUNCH_RULE(0, true, false);
+    // (LAUNCH_RULE: the orbital twin of the build when the context's rule is the orbital one; LAUNCH_LIGHT: of either, the
+    // one-light twin when the scene has one light)
+    case Build::V4_F0_STAMPS: LAUNCH_LIGHT(true, true); case Build::V4_F0: LAUNCH_LIGHT(true, false);
     case Build::V4_F3_STAMPS: LAUNCH(k_mutate_v4<3, true, true>); case Build::V4_F3: LAUNCH_RULE(3, true, false); case Build::V4_F7: LAUNCH_RULE(7, true, false);
     case Build::V4_F15_S32: LAUNCH(k_mutate_v4<15, true, false, false, true>); case Build::V4_F15_OVF: LAUNCH(k_mutate_v4<15, true, false, true, true>);
     case Build::V4_F15: LAUNCH(k_mutate_v4<15, true, false, true>);            case Build::V4_F7_GLOBAL: LAUNCH(k_mutate_v4<7, false, false>);
@@ -1515,6 +1531,7 @@ void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint
         fprintf(stderr, "[drmlt] launch_mutate: build %d is not a technique=path kernel\n", (int) plan.build);
         abort();
     }
+#undef LAUNCH_LIGHT
 #undef LAUNCH_RULE
 #undef LAUNCH
 }

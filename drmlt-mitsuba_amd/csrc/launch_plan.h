@@ -49,7 +49,8 @@ struct Knobs {
     size_t bdpt_lds_pad = 0;                 // DRMLT_BDPT_LDS_PAD: extra LDS bytes of every bdpt kernel (occupancy experiments)
     bool no_run_ahead = false;               // DRMLT_NO_RUN_AHEAD
     bool rule_generic = false;               // DRMLT_RULE_GENERIC: k_mutate_v4 runs its generic body whatever the rule (device_types.h: rule_is_orbital)
-    long long ahead_cap = -1;                // DRMLT_AHEAD_CAP: mutations a chain may run beyond the launch's target; -1 = min(8 slices, 8192)
+    bool one_light_generic = false;          // DRMLT_ONE_LIGHT_GENERIC: k_mutate_v4 reads the light from the staged tables however many the scene has (device_types.h: scene_has_one_light)
+    long long ahead_cap = -1;               // DRMLT_AHEAD_CAP: mutations a chain may run beyond the launch's target; -1 = min(8 slices, 8192)
     bool mmlt_no_sort = false, no_regroup = false, regroup_on_host = false, regroup_check = false; // DRMLT_MMLT_NO_SORT, _NO_REGROUP, _REGROUP_ON_HOST, _REGROUP_CHECK
     int regroup_first = 0;                   // DRMLT_REGROUP_FIRST: length of a call's first launch when regrouping, 1..slice; 0 = by the call
 };
@@ -60,7 +61,7 @@ inline Knobs read_knobs() {
         {"DRMLT_VERBOSE", &K.verbose}, {"DRMLT_BVH_STACK32", &K.bvh_stack32}, {"DRMLT_NO_QUAD_MERGE", &K.no_quad_merge}, {"DRMLT_NO_BOX_MERGE", &K.no_box_merge},
         {"DRMLT_NO_FLAT_LOOP", &K.no_flat_loop}, {"DRMLT_FEAT_ALL", &K.feat_all}, {"DRMLT_NO_SMALL_TABLES", &K.no_small_tables},
         {"DRMLT_MMLT_TABLES_GLOBAL", &K.mmlt_tables_global}, {"DRMLT_BDPT_TABLES_GLOBAL", &K.bdpt_tables_global}, {"DRMLT_NO_RUN_AHEAD", &K.no_run_ahead},
-        {"DRMLT_RULE_GENERIC", &K.rule_generic},
+        {"DRMLT_RULE_GENERIC", &K.rule_generic}, {"DRMLT_ONE_LIGHT_GENERIC", &K.one_light_generic},
         {"DRMLT_MMLT_NO_SORT", &K.mmlt_no_sort}, {"DRMLT_NO_REGROUP", &K.no_regroup}, {"DRMLT_REGROUP_ON_HOST", &K.regroup_on_host}, {"DRMLT_REGROUP_CHECK", &K.regroup_check}};
     for (const auto &f : flags) *f.on = getenv(f.name) != nullptr;
     int v = 0;

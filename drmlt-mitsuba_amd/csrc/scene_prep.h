@@ -495,7 +495,9 @@ inline std::string prepare_scene(const drmlt_config &cfg, const drmlt_scene &sce
         P.eff_dim = P.mmlt_S + P.mmlt_E + P.bd_Dd;
     }
 
-    P.debug = K.debug | (K.rule_generic ? DBG_RULE_GENERIC : 0);
+    P.debug = K.debug | (K.rule_generic ? DBG_RULE_GENERIC : 0) | (K.one_light_generic ? DBG_ONE_LIGHT_GENERIC : 0);
+    // the first light's joined record (device_types.h: scene_has_one_light decides whether a kernel reads it)
+    if (!out.emitters.empty()) { P.light = out.emitters[0]; P.light_shade = out.shade[(size_t) out.emitters[0].prim]; }
     for (const DBsdf &b : out.bsdfs) P.features |= b.type == DRMLT_BSDF_ROUGHCONDUCTOR ? 1 : ((b.type == DRMLT_BSDF_DIELECTRIC || b.type == DRMLT_BSDF_CONDUCTOR) ? 2 : 0);
     for (const DPrim &g : out.prims) if (g.type == PRIM_SPHERE) P.features |= 4;
     P.env_emitter = -1;
