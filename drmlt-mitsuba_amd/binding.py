@@ -29,6 +29,7 @@ ABI_SYMBOLS = (
     "drmlt_node_create", "drmlt_node_seed", "drmlt_node_run", "drmlt_node_develop", "drmlt_node_stats_get",
     "drmlt_node_set_importance_map", "drmlt_node_device_count", "drmlt_node_context", "drmlt_node_last_error",
     "drmlt_node_destroy", "drmlt_bootstrap_luminances", "drmlt_seed_indices", "drmlt_comm_info", "drmlt_film_tile",
+    "drmlt_render_direct", "drmlt_direct_split", "drmlt_node_render_direct",
 )
 
 
@@ -104,6 +105,9 @@ def load_library():
     L.drmlt_seed_indices.argtypes = [C.c_void_p, C.c_void_p]
     L.drmlt_comm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.drmlt_film_tile.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.drmlt_render_direct.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p]
+    L.drmlt_direct_split.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.drmlt_node_render_direct.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]
     _lib = L
     return L
 
@@ -293,6 +297,15 @@ class Context:
         self._chk(self.L.drmlt_render_pt(self.h, spp, seed, out.ctypes.data))
         return out
 
+    def render_direct(self, direct_samples=None, hide_emitters=False, seed=1, rows=None):
+        """The direct-illumination image develop(direct=...) adds (renderDirectComponent): rows [rows[0], rows[1]) of it, the
+        whole frame by default. direct_samples defaults to the configuration's."""
+        n = self.cfg.direct_samples if direct_samples is None else direct_samples
+        lo, hi = (0, self.height) if rows is None else rows
+        out = np.empty((max(hi - lo, 0), self.width, 3), dtype=np.float32)
+        self._chk(self.L.drmlt_render_direct(self.h, n, int(bool(hide_emitters)), seed, lo, hi, out.ctypes.data))
+        return out
+
     def chain_state(self, dim):
         n = self.stats().n_chains
         cur = (abi.Splat * n)()
@@ -345,6 +358,16 @@ def film_tile(height, rank, world):
     if rc != 0:
         raise DrmltError(rc, "no valid partition of %d rows over %d ranks (rank %d)" % (height, world, rank))
     return lo.value, hi.value, rows.value
+
+
+def direct_split(direct_samples):
+    """(pixelSamples, shadingSamples) of the direct pass for `directSamples` (util.cpp:40-54): the library's own arithmetic, no device."""
+    L = load_library()
+    ps, ss = C.c_int32(), C.c_int32()
+    rc = L.drmlt_direct_split(direct_samples, C.byref(ps), C.byref(ss))
+    if rc != 0:
+        raise DrmltError(rc, "directSamples must be positive (got %d): no direct image is rendered" % direct_samples)
+    return ps.value, ss.value
 
 
 def comm_unique_id():
@@ -403,6 +426,13 @@ class Node:
         out = np.empty((self.height, self.width, 3), dtype=np.float32)
         d = np.ascontiguousarray(direct, dtype=np.float32) if direct is not None else None
         self._chk(self.L.drmlt_node_develop(self.h, d.ctypes.data if d is not None else None, out.ctypes.data))
+        return out
+
+    def render_direct(self, direct_samples=None, hide_emitters=False, seed=1):
+        """Context.render_direct for the full frame, the rows split over the node's ranks (film_tile)."""
+        n = self.cfg.direct_samples if direct_samples is None else direct_samples
+        out = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        self._chk(self.L.drmlt_node_render_direct(self.h, n, int(bool(hide_emitters)), seed, out.ctypes.data))
         return out
 
     def set_importance_map(self, lum_map):

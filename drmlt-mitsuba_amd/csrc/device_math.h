@@ -62,4 +62,4 @@ DEV float pick4(u4 b, uint32_t i) {
 }
 
 // stream tags: counter word 3 (DESIGN.md "RNG addressing"; same numbering as oracle_sampler.hpp)
-enum : uint32_t { TAG_BOOT = 0, TAG_SEEDSEL = 1, TAG_COIN = 2, TAG_S1 = 3, TAG_S2 = 4, TAG_PT = 5 };
+enum : uint32_t { TAG_BOOT = 0, TAG_SEEDSEL = 1, TAG_COIN = 2, TAG_S1 = 3, TAG_S2 = 4, TAG_PT = 5, TAG_DIRECT = 6 };

@@ -200,6 +200,19 @@ constexpr bool scene_has_one_light(const DParams &P) {
            ((P.light_shade.bsdf >> 24) == PRIM_RECTANGLE || (P.light_shade.bsdf >> 24) == PRIM_TRIANGLE) && (P.debug & DBG_ONE_LIGHT_GENERIC) == 0;
 }
 
+// The direct-illumination pass (kernels_direct.hip, device_direct.h): what its launch carries besides the context's parameter block.
+// A kernel argument of its own: no field of DParams, so no chain kernel sees it.
+struct DirectJob {
+    uint32_t key0, key1;
+    int32_t pixel_samples, shading_samples; // util.cpp:40-54 (film_tiles.h: direct_split)
+    int32_t group_log2;                     // a pixel's samples sit in 2^group_log2 adjacent lanes (>= pixel_samples)
+    int32_t hide_emitters;
+    int32_t row_lo, row_hi;                 // rows of the image that `acc` holds
+    int32_t samp_lo, samp_hi;               // rows whose samples are drawn: the above widened by `margin`, clipped to the image
+    int32_t margin;                         // ceil(filter radius - 1/2): how far a sample's footprint reaches beyond its own pixel
+    float *acc;                             // [row_hi - row_lo][W][4]: sum of w rgb, sum of w
+};
+
 // result of one PSS evaluation, SoA-friendly
 struct DSplat {
     float lum, px, py, r, g, b;

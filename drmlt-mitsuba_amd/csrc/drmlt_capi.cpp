@@ -37,6 +37,9 @@ void launch_init_chains_bdpt(const DParams &P, const uint32_t *seed_index, const
 void launch_mutate_bdpt(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
 void launch_eval_lists_bdpt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out, uint32_t stride, size_t lds, hipStream_t st);
 void launch_render_pt(const DParams &P, uint64_t n_samples, uint32_t stream, float scale, hipStream_t st);
+// the direct-illumination pass (kernels_direct.hip)
+uint32_t direct_grid(const DirectJob &J, int width);
+void launch_render_direct(const DParams &P, const DirectJob &J, float *out, hipStream_t st);
 
 namespace {
 
@@ -803,6 +806,48 @@ int drmlt_render_pt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb)
     launch_render_pt(P, n, 0u, 1.0f / (float) spp, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out_rgb, film.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DRMLT_OK;
+}
+
+int drmlt_direct_split(int32_t direct_samples, int32_t *pixel_samples, int32_t *shading_samples) {
+    int ps = 0, ss = 0;
+    if (!pixel_samples || !shading_samples || !direct_split(direct_samples, ps, ss)) return DRMLT_E_INVALID;
+    *pixel_samples = ps; *shading_samples = ss;
+    return DRMLT_OK;
+}
+
+// BidirectionalUtils::renderDirectComponent (util.cpp:30-92) for rows [row_lo, row_hi). Under a filter wider than a pixel the rows
+// just outside the range are sampled too (their footprints reach in); their random numbers are addressed by the pixel, so they are
+// the very samples the neighbouring range draws. The context's film, chains and parameter block are left alone.
+int drmlt_render_direct(drmlt_ctx *ctx, int32_t direct_samples, int32_t hide_emitters, uint64_t seed, int32_t row_lo, int32_t row_hi, float *out_rgb) {
+    if (!ctx) return DRMLT_E_INVALID;
+    if (!out_rgb) return ctx->fail(DRMLT_E_INVALID, "render_direct: out_rgb is NULL");
+    DirectJob J{};
+    if (!direct_split(direct_samples, J.pixel_samples, J.shading_samples))
+        return ctx->fail(DRMLT_E_INVALID, "render_direct: directSamples must be positive (got %d); the chains carry the direct light when it is -1", (int) direct_samples);
+    const DParams &P = ctx->P;
+    if (row_lo < 0 || row_hi > P.height || row_lo >= row_hi)
+        return ctx->fail(DRMLT_E_INVALID, "render_direct: rows [%d, %d) are not a non-empty range within the film's %d rows", (int) row_lo, (int) row_hi, P.height);
+    while ((1 << J.group_log2) < J.pixel_samples) J.group_log2++;
+    J.key0 = (uint32_t) seed; J.key1 = (uint32_t) (seed >> 32);
+    J.hide_emitters = hide_emitters ? 1 : 0;
+    J.row_lo = row_lo; J.row_hi = row_hi;
+    J.margin = std::max(0, (int) std::ceil(P.filter_radius - 0.5f));
+    J.samp_lo = std::max(0, row_lo - J.margin); J.samp_hi = std::min(P.height, row_hi + J.margin);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the workspace first: 4-channel film of the rows + the developed rows; nothing is allocated once the launches are enqueued
+    const size_t n_out = (size_t) (row_hi - row_lo) * P.width;
+    DevBuf acc, out;
+    HIP_TRY(ctx, acc.alloc(n_out * 4 * sizeof(float)));
+    HIP_TRY(ctx, out.alloc(n_out * 3 * sizeof(float)));
+    DParams Pl = P;
+    HIP_TRY(ctx, ensure_overflow(ctx, Pl, (size_t) direct_grid(J, P.width) * 64));
+    J.acc = acc.as<float>();
+    HIP_TRY(ctx, hipMemsetAsync(acc.p, 0, acc.bytes, ctx->stream));
+    launch_render_direct(Pl, J, out.as<float>(), ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, out.p, out.bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DRMLT_OK;
 }

@@ -482,6 +482,21 @@ int drmlt_node_develop(drmlt_node *node, const float *direct_rgb_or_null, float 
     return rc_all;
 }
 
+// The direct image of the whole frame: rank r renders the rows of its film tile, all ranks at once, each on its own stream, straight
+// into the caller's frame. A sample is addressed by its pixel, so the frame is the one a single context renders.
+int drmlt_node_render_direct(drmlt_node *node, int32_t direct_samples, int32_t hide_emitters, uint64_t seed, float *out_rgb) {
+    if (!node) return DRMLT_E_INVALID;
+    if (!out_rgb) return node->fail(DRMLT_E_INVALID, "render_direct: out_rgb is NULL");
+    const int n = (int) node->subs.size();
+    return for_each_rank(node, [&](int r) {
+        drmlt_ctx *c = node->subs[r];
+        int lo, hi;
+        tile_range(c, r, n, lo, hi);
+        if (lo >= hi && direct_samples > 0) return (int) DRMLT_OK; // more ranks than rows: nothing to render (a bad sample count is still refused)
+        return drmlt_render_direct(c, direct_samples, hide_emitters, seed, lo, hi, out_rgb + (size_t) lo * c->P.width * 3);
+    });
+}
+
 int drmlt_node_stats_get(drmlt_node *node, drmlt_stats *out) {
     if (!node || !out) return DRMLT_E_INVALID;
     memset(out, 0, sizeof *out);

@@ -38,3 +38,17 @@ struct ChainRange { unsigned first, count, pool; };
 inline ChainRange chain_range(unsigned per_rank, int rank, int world) {
     return ChainRange{(unsigned) rank * per_rank, per_rank, per_rank * (unsigned) world};
 }
+
+// Sample split of the direct-illumination pass (BidirectionalUtils::renderDirectComponent, src/libbidir/util.cpp:40-54): directSamples
+// samples per pixel become pixelSamples camera rays with shadingSamples emitter and BSDF samples each.
+// false: directSamples <= 0 (no direct image is rendered).
+inline bool direct_split(int direct_samples, int &pixel_samples, int &shading_samples) {
+    if (direct_samples <= 0) return false;
+    pixel_samples = direct_samples;
+    shading_samples = 1;
+    while (pixel_samples > 8) {
+        pixel_samples /= 2;
+        shading_samples *= 2;
+    }
+    return true;
+}

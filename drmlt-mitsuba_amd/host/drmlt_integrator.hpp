@@ -191,9 +191,16 @@ public:
         }
         bool ok = rc == DRMLT_OK;
         std::string msg;
+        // the direct image (drmlt.cpp:479, the outer render only: the nested first stage above has none), added by develop
+        std::vector<float> direct;
+        if (ok && m_cfg.direct_samples > 0) {
+            direct.resize((size_t) sc.camera.width * sc.camera.height * 3);
+            rc = drmlt_render_direct(ctx, m_cfg.direct_samples, 0, m_seed, 0, sc.camera.height, direct.data());
+            ok = rc == DRMLT_OK;
+        }
         if (ok) {
             out.assign((size_t) sc.camera.width * sc.camera.height * 3, 0.f);
-            rc = drmlt_develop(ctx, nullptr, out.data());
+            rc = drmlt_develop(ctx, direct.empty() ? nullptr : direct.data(), out.data());
             ok = rc == DRMLT_OK;
         }
         if (!ok && rc != DRMLT_E_CANCELLED) msg = drmlt_last_error(ctx);

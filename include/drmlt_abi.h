@@ -313,6 +313,24 @@ int drmlt_kernel_time(drmlt_ctx *ctx, double *avg_ms, uint64_t *launches, int re
  * (test utility: equal-expectation reference for the MLT image). */
 int drmlt_render_pt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb);
 
+/* The direct-illumination image that develop adds when directSamples > 0
+ * (BidirectionalUtils::renderDirectComponent, src/libbidir/util.cpp:30-92, with
+ * MIDirectIntegrator::Li, src/integrators/direct/direct.cpp:146-314): the
+ * chains of such a context carry indirect light only.
+ * out_rgb: (row_hi - row_lo) * W * 3 floats, rows [row_lo, row_hi) of the direct image.
+ * direct_samples is split into pixel and shading samples as util.cpp:40-54 does
+ * (drmlt_direct_split: pure arithmetic, no device). hide_emitters is direct.cpp's
+ * own property (the reference leaves it 0): directly visible emitters and the
+ * environment behind the scene stay black. The image is a function of the
+ * arguments alone -- every sample's random numbers are addressed by (seed,
+ * pixel, sample) -- so row ranges tile a frame exactly. Works on a context of
+ * any technique; does not touch the chain film or the chain state.
+ * DRMLT_E_INVALID: direct_samples <= 0, an empty or out-of-range row range,
+ * NULL pointers. */
+int drmlt_render_direct(drmlt_ctx *ctx, int32_t direct_samples, int32_t hide_emitters,
+                        uint64_t seed, int32_t row_lo, int32_t row_hi, float *out_rgb);
+int drmlt_direct_split(int32_t direct_samples, int32_t *pixel_samples, int32_t *shading_samples);
+
 /* Bootstrap inspection (test utilities for the seed-selection parity test): the luminance samples of
  * generateSeeds' first loop (pathsampler.cpp:879-920) for bootstrap stream `stream`, and the sample indices the last
  * drmlt_seed / drmlt_seed_pool picked for this context's chains (sorted, n_chains values). */
@@ -390,6 +408,9 @@ int drmlt_node_seed(drmlt_node *node, uint64_t seed, double *b_out);
 int drmlt_node_run(drmlt_node *node, uint64_t total_mutations, volatile int *stop,
                    drmlt_progress_cb cb, void *user);
 int drmlt_node_develop(drmlt_node *node, const float *direct_rgb_or_null, float *out_rgb);
+/* drmlt_render_direct for the full frame: rank r renders the rows of its film tile (drmlt_film_tile), all ranks concurrently. */
+int drmlt_node_render_direct(drmlt_node *node, int32_t direct_samples, int32_t hide_emitters,
+                             uint64_t seed, float *out_rgb);
 int drmlt_node_stats_get(drmlt_node *node, drmlt_stats *out);
 int drmlt_node_set_importance_map(drmlt_node *node, const float *lum_map_or_null);
 int drmlt_node_device_count(drmlt_node *node);
