@@ -36,7 +36,8 @@ class Config(C.Structure):
 
 
 class Shape(C.Structure):
-    _fields_ = [("type", C.c_int32), ("bsdf", C.c_int32), ("emitter", C.c_int32), ("reserved", C.c_int32),
+    _fields_ = [("type", C.c_int32), ("bsdf", C.c_int32), ("emitter", C.c_int32),
+                ("normals", C.c_int32),   # 0: face normal; k >= 1: entry k - 1 of Scene.normals (triangles, technique=path)
                 ("data", C.c_float * 12)]
 
 
@@ -59,11 +60,14 @@ class Scene(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_shapes", C.c_int32), ("n_bsdfs", C.c_int32),
                 ("n_emitters", C.c_int32), ("shapes", C.POINTER(Shape)), ("bsdfs", C.POINTER(Bsdf)),
                 ("emitters", C.POINTER(Emitter)), ("camera", Camera),
-                ("n_points", C.c_int32), ("points", C.POINTER(C.c_float))]
+                ("n_points", C.c_int32), ("points", C.POINTER(C.c_float)),
+                ("n_normals", C.c_int32), ("normals", C.POINTER(C.c_float))]
 
 
 # struct_size of a drmlt_scene that ends at `camera` (no point lights): include/drmlt_abi.h, DRMLT_SCENE_SIZE_NO_POINTS
 SCENE_SIZE_NO_POINTS = (Scene.camera.offset + C.sizeof(Camera) + C.sizeof(C.c_void_p) - 1) // C.sizeof(C.c_void_p) * C.sizeof(C.c_void_p)
+# ... and of one that ends at `points` (no vertex normals): DRMLT_SCENE_SIZE_NO_NORMALS
+SCENE_SIZE_NO_NORMALS = Scene.points.offset + C.sizeof(C.c_void_p)
 
 
 class Stats(C.Structure):

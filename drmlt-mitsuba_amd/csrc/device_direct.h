@@ -42,10 +42,12 @@ DEV f3 direct_emitter_sample(const DParams &P, const TablesT &T, const DBsdf &B,
     const DShade L = T.emitter_shade(ei, E);
     const int kind = L.bsdf >> 24;
     f3 lp;
+    float lu = 0.f, lv = 0.f; // a triangle's sample: barycentrics of p1 and p2
     if (kind == PRIM_RECTANGLE) lp = fma3(ld3(L.eu), sx, fma3(ld3(L.ev), sy, ld3(L.origin))); // rectangle.cpp:210-216
     else if ((FEAT & 4) && kind == PRIM_POINT) lp = ld3(L.origin);                            // point.cpp:131-151
-    else { const float a = sqrtf(fmaxf(0.f, 1.f - sx)); lp = fma3(ld3(L.eu), 1.f - a, fma3(ld3(L.ev), a * sy, ld3(L.origin))); } // squareToUniformTriangle
+    else { const float a = sqrtf(fmaxf(0.f, 1.f - sx)); lu = 1.f - a; lv = a * sy; lp = fma3(ld3(L.eu), lu, fma3(ld3(L.ev), lv, ld3(L.origin))); } // squareToUniformTriangle
     f3 ln = ld3(L.n);
+    if ((FEAT & 4) && kind == PRIM_SMOOTH) smooth_record_normal(P, lu, lv, ln); // triangle.cpp:34-42: the interpolated normal; zero: pdf = 0 below
     const f3 dv = lp - p;
     const float dist2 = dot3(dv, dv);
     dist = sqrtf(dist2);
@@ -130,6 +132,7 @@ DEV f3 direct_bsdf_sample(const DParams &P, const TablesT &T, const DBsdf &B, bo
         f3 en = ld3(S.n);
         const bool sphere = (FEAT & 4) && (S.bsdf >> 24) == PRIM_SPHERE;
         if (sphere) en = normalize3(fma3(d, h.t, p) - ld3(S.origin));
+        if ((FEAT & 4) && (S.bsdf >> 24) == PRIM_SMOOTH) smooth_record_normal(P, h.u, h.v, en); // its.shFrame.n; zero: dn = 0, nothing
         const float dn = dot3(d, en);
         if (!(dn < 0.f)) return zero; // AreaLight::eval: dot(n, -d) > 0
         const DEmitter E = T.emitter(S.emitter);
@@ -160,6 +163,8 @@ DEV f3 direct_li(const DParams &P, const TablesT &T, const DirectJob &J, f3 o, f
         p = fma3(ld3(S.eu), h.u, fma3(ld3(S.ev), h.v, ld3(S.origin)));
         n = ld3(S.n);
         s = ld3(S.eu) * S.inv_len_eu;
+        // vertex normals (skdtree.h:355-396,426); a normal without a direction makes the sample invalid
+        if ((FEAT & 4) && (S.bsdf >> 24) == PRIM_SMOOTH && !smooth_record_frame(P, h.u, h.v, n, s)) return mk3(0.f, 0.f, 0.f);
     } else {
         const f3 c = ld3(S.origin);
         const f3 local = normalize3(fma3(d, h.t, o) - c);

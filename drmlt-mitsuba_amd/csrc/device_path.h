@@ -33,6 +33,44 @@ template <class T> DEV T load_global16(const T *p) {
     for (unsigned i = 0; i < sizeof(T) / 16u; ++i) u.w[i] = q[i];
     return u.v;
 }
+// Shading frame of a PRIM_SMOOTH record at the barycentrics (u, v) of p1 and p2 (smooth_frame.h; the hit of path_step and direct_li,
+// and -- for its normal alone -- the light samples and emitter hits of both). In: n.x = the record's `n[0]`, which holds the index of
+// its table entry; s = a positive multiple of p1 - p0 (the flat primitives' tangent). Out: the frame, or n = s = 0 and false: the
+// interpolated normal has no direction, the caller ends the path. The entry is fetched by the lanes that hold such a record from
+// device memory in every build: a plain per-lane gather behind the caller's kind test, which a wave without a smooth triangle
+// skips as a whole. The step's builds sit at their register limits, so the routine is written to need next to nothing beside
+// what the step holds anyway: it takes the index where the flat normal lies, and the entry's three 16-byte words arrive and are
+// consumed one after the other (the empty asm keeps the next load behind the sum).
+DEV f3 smooth_record_sum(const DParams &P, float index_bits, float u, float v) {
+    // a wave-uniform base and a 32-bit byte offset per lane (global_load ... v_off, s[base]): one address register, three dwords a word
+    typedef float f32x3_t __attribute__((ext_vector_type(3)));
+    typedef const char __attribute__((address_space(1))) *GB;
+    typedef const f32x3_t __attribute__((address_space(1))) *GQ;
+    const GB q = (GB) (uintptr_t) P.normals + (__float_as_uint(index_bits) - SMOOTH_INDEX_BIAS) * (uint32_t) sizeof(DSmooth);
+    const f32x3_t w0 = *(GQ) q;
+    f3 a = mk3(w0.x, w0.y, w0.z);
+    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z) : : "memory");
+    const f32x3_t w1 = *(GQ) (q + 16);
+    a = fma3(mk3(w1.x, w1.y, w1.z), u, a);
+    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z) : : "memory");
+    const f32x3_t w2 = *(GQ) (q + 32);
+    a = fma3(mk3(w2.x, w2.y, w2.z), v, a);
+    return a;
+}
+DEV bool smooth_record_frame(const DParams &P, float u, float v, f3 &n, f3 &s) {
+    const f3 a = smooth_record_sum(P, n.x, u, v);
+    const SmoothFrame F = smooth_finish(a.x, a.y, a.z, s.x, s.y, s.z);
+    n = mk3(F.nx, F.ny, F.nz);
+    s = mk3(F.sx, F.sy, F.sz);
+    return !is_zero3(n);
+}
+// The normal alone, for an area light's sample and an emitter hit: in n.x the index, out the unit normal, or 0 when it has no
+// direction (the light sample's pdf is then 0, the hit's cosine 0). No tangent takes part.
+DEV void smooth_record_normal(const DParams &P, float u, float v, f3 &n) {
+    const f3 a = smooth_record_sum(P, n.x, u, v);
+    const SmoothFrame F = smooth_finish_normal(a.x, a.y, a.z);
+    n = mk3(F.nx, F.ny, F.nz);
+}
 // Samplers whose components are plain reads (proposal rows in LDS or in device memory) have the draws of a path step requested
 // together: a loop over `need` reads, each waited for, was `need` LDS round trips per step even with the rows in LDS (round 4: config 2
 // 2.11e9 -> 2.24e9, the 2000-triangle soup 5.82e8 -> 6.01e8; with the rows in device memory it is the difference between one and five
@@ -936,6 +974,11 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
             p = fma3(ld3(S.eu), hit.u, fma3(ld3(S.ev), hit.v, ld3(S.origin)));
             n = ld3(S.n);
             s = ld3(S.eu) * S.inv_len_eu;
+            // vertex normals: the interpolated normal and computeShadingFrame's tangent replace both (skdtree.h:355-396,426); a normal
+            // without a direction makes the sample invalid (f = 0)
+            // (a normal without a direction comes back as n = s = 0 and ends the path below, where the BSDF is read: an exit of its own
+            // here cost every build with bit 4 some ten registers)
+            if ((FEAT & 4) && __builtin_expect(ptype == PRIM_SMOOTH, 0)) smooth_record_frame(P, hit.u, hit.v, n, s);
         } else {
             f3 c = ld3(S.origin);
             f3 local = normalize3(fma3(ps.d, hit.t, ps.o) - c);
@@ -983,6 +1026,12 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
         ps.o = p; ps.n = n; ps.s = s;
         ps.bsdf = S.bsdf & 0xffffff;
         B = T.bsdf(ps.bsdf);
+        // a smooth triangle whose interpolated normal has no direction: the sample is invalid (f = 0). wi = 0, no light sample passes
+        // its wo.z > 0, and as a diffuse vertex the path ends at that branch's wi.z > 0 -- the exits the step already has
+        if ((FEAT & 4) && is_zero3(n)) {
+            B.type = 0;
+            ps.Li = mk3(0.f, 0.f, 0.f);
+        }
         ps.refn_zero = (FEAT & 2) && B.type == 1; // transmissive / two-sided: DirectSamplingRecord(its) zeroes refN
         // no light sample at a delta vertex, dielectric or smooth conductor (path.cpp:187, the ESmooth gate)
         want_nee = ps.direct_on && (B.type == 0 || ((FEAT & 1) && B.type == 2));
@@ -1037,6 +1086,10 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
                 lp = fma3(ld3(L.eu), 1.f - a, fma3(ld3(L.ev), a * sy, ld3(L.origin)));
             }
             f3 ln = ld3(L.n);
+            if ((FEAT & 4) && __builtin_expect((L.bsdf >> 24) == PRIM_SMOOTH, 0)) { // Triangle::sample returns the interpolated normal (triangle.cpp:34-42); zero: pdf = 0 below
+                const float a = sqrtf(fmaxf(0.f, 1.f - sx)); // the sample's barycentrics (1 - a, a sy), formed again: sx and sy live on anyway
+                smooth_record_normal(P, 1.f - a, a * sy, ln);
+            }
             f3 dv = lp - p;
             float dist2 = dot3(dv, dv), dist = sqrtf(dist2);
             f3 dd = dv * (1.f / dist);

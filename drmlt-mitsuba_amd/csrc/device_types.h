@@ -11,6 +11,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "smooth_frame.h"
+
 #define DRMLT_MAX_LDS_PRIMS 96
 #define BDPT_MAX_DEPTH 24 // technique=bdpt: one wave's LDS rows (samplers + densities, device_bdpt.h) reach the 64 KB a workgroup may have at maxDepth 26; the flag words would hold 31
 
@@ -19,7 +21,11 @@
 // PRIM_POINT: kind tag of a point light's shading record only (position in `origin`), appended after the primitives' records and
 // reached through DEmitter::prim; no intersection record carries it
 // PRIM_ENV: the same for the constant environment emitter (the scene's bounding sphere: centre in `origin`, radius in eu[0])
-enum { PRIM_TRIANGLE = 0, PRIM_RECTANGLE = 1, PRIM_SPHERE = 2, PRIM_QUAD2 = 3, PRIM_POINT = 4, PRIM_ENV = 5 };
+// PRIM_SMOOTH: kind tag of the shading record of a triangle with vertex normals. Its intersection record is a PRIM_TRIANGLE's (the
+// ray loops, the flat records and the BVH do not know it); where a flat primitive's shading record has its normal, this one has
+// the index of its entry in DParams::normals (the bits of n[0], biased so that they are a normal float: smooth_frame.h, which
+// also builds the frame). inv_len_eu is a triangle's.
+enum { PRIM_TRIANGLE = 0, PRIM_RECTANGLE = 1, PRIM_SPHERE = 2, PRIM_QUAD2 = 3, PRIM_POINT = 4, PRIM_ENV = 5, PRIM_SMOOTH = 6 };
 
 // World -> primitive space affine map (rows), so that one transform serves all three
 // primitive kinds: triangle -> barycentric (u,v,w); rectangle -> Mitsuba object space
@@ -56,7 +62,7 @@ struct DShade {
     float origin[3]; // tri: p0; rect: centre; sphere: centre; point light: position; environment: bounding sphere's centre
     float eu[3];     // tri: p1-p0; rect: objectToWorld column 0; sphere, environment: eu[0] = radius
     float ev[3];     // tri: p2-p0; rect: objectToWorld column 1
-    float n[3];      // unit geometric (= shading) normal of flat primitives
+    float n[3];      // unit geometric (= shading) normal of flat primitives; PRIM_SMOOTH: n[0] = the bits of the index into DParams::normals
     float inv_len_eu;
     int32_t bsdf;
     int32_t emitter; // -1: none
@@ -125,7 +131,7 @@ struct DParams {
     int32_t *error_flag;
     int32_t debug;          // DRMLT_DEBUG bit mask (diagnostics only)
     int32_t kernel_variant; // technique=path's chain kernel (launch_plan.h): 3 k_mutate_v3 (cross-check), 4 k_mutate_v4 (lane pairs), 5 k_mutate_v5 (ray pool)
-    int32_t features;       // bit 0 rough conductor, bit 1 delta BSDFs (dielectric, smooth conductor), bit 2 what is not a polygon (spheres, point lights, environment), bit 3 BVH traversal needed
+    int32_t features;       // bit 0 rough conductor, bit 1 delta BSDFs (dielectric, smooth conductor), bit 2 what is not a flat polygon (spheres, point lights, environment, triangles with vertex normals), bit 3 BVH traversal needed
     int32_t mh_batch;       // k_mutate_v4 / v5: parked chains needed before the bookkeeping branch is taken
     // technique=mmlt (device_bidir.h)
     int32_t technique;        // DRMLT_TECH_*
@@ -172,6 +178,9 @@ struct DParams {
     // A section's own copy of the block delivers them as scalar loads (device_path.h: OneLightTables; scene_has_one_light below)
     DEmitter light;
     DShade light_shade;
+    // vertex normals of the PRIM_SMOOTH shading records (read under feature bit 4 only, once per hit or light sample by the lanes
+    // that hold such a record; device memory in every build), or NULL. Last: no offset of the fields above moves.
+    const DSmooth *normals;
 };
 
 // Compile-time rule tag of the chain loop (k_mutate_v4's bodies; mh_digest and RowSampler take it as a template parameter).

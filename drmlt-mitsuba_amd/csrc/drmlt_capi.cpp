@@ -97,12 +97,19 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
         return nullptr;
     };
     if (!cfg || !scene) return bail(nullptr, "null config or scene");
-    if (cfg->struct_size != sizeof(drmlt_config) || (scene->struct_size != sizeof(drmlt_scene) && scene->struct_size != DRMLT_SCENE_SIZE_NO_POINTS))
+    if (cfg->struct_size != sizeof(drmlt_config) || (scene->struct_size != sizeof(drmlt_scene) && scene->struct_size != DRMLT_SCENE_SIZE_NO_NORMALS && scene->struct_size != DRMLT_SCENE_SIZE_NO_POINTS))
         return bail(nullptr, "struct_size mismatch (ABI version skew)");
-    // a scene that ends at `camera` has no point lights: nothing behind `camera` is read (its tail padding is where n_points lies)
+    // a scene that ends at `camera` has no point lights: nothing behind `camera` is read (its tail padding is where n_points lies);
+    // one that ends at `points` has no vertex normals, and neither reads drmlt_shape.normals: to those callers it is `reserved`
     drmlt_scene scene_in;
     memset(&scene_in, 0, sizeof scene_in);
-    memcpy(&scene_in, scene, scene->struct_size == sizeof(drmlt_scene) ? sizeof(drmlt_scene) : offsetof(drmlt_scene, camera) + sizeof(drmlt_camera));
+    memcpy(&scene_in, scene, scene->struct_size == sizeof(drmlt_scene) ? sizeof(drmlt_scene) : scene->struct_size == DRMLT_SCENE_SIZE_NO_NORMALS ? (size_t) DRMLT_SCENE_SIZE_NO_NORMALS : offsetof(drmlt_scene, camera) + sizeof(drmlt_camera));
+    std::vector<drmlt_shape> shapes_in;
+    if (scene->struct_size != sizeof(drmlt_scene) && scene->shapes && scene->n_shapes > 0) {
+        shapes_in.assign(scene->shapes, scene->shapes + scene->n_shapes);
+        for (drmlt_shape &sh : shapes_in) sh.normals = 0;
+        scene_in.shapes = shapes_in.data();
+    }
     scene = &scene_in;
     // ---- parameter checks of the DRMLT ctor / PathSampler ctor (drmlt.cpp:193-349, pathsampler.cpp:57-71)
     if (cfg->algo != DRMLT_ALGO_DRMLT && cfg->algo != DRMLT_ALGO_PSSMLT) return bail(nullptr, "Unknown algorithm");
@@ -167,11 +174,13 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
         return v.empty() || (b.alloc(std::max<size_t>(bytes, 64)) == hipSuccess && hipMemcpy(b.p, v.data(), bytes, hipMemcpyHostToDevice) == hipSuccess);
     };
     bool ok = up(ctx->d_prims, prep.prims) && up(ctx->d_shade, prep.shade) && up(ctx->d_bsdfs, prep.bsdfs) && up(ctx->d_emitters, prep.emitters) &&
-              up(ctx->d_lut, prep.lut) && up(ctx->d_bvh, prep.bvh) && up(ctx->d_prims_flat, prep.flat) && up(ctx->d_prims_box, prep.boxes);
+              up(ctx->d_lut, prep.lut) && up(ctx->d_bvh, prep.bvh) && up(ctx->d_prims_flat, prep.flat) && up(ctx->d_prims_box, prep.boxes) &&
+              up(ctx->d_normals, prep.normals);
     if (!ok) return bail(ctx, "device allocation/upload of the scene failed");
     P.prims = ctx->d_prims.as<DPrim>(); P.shade = ctx->d_shade.as<DShade>(); P.bsdfs = ctx->d_bsdfs.as<DBsdf>();
     P.emitters = ctx->d_emitters.as<DEmitter>(); P.bvh = ctx->d_bvh.as<DBvh4Node>(); P.filter_lut = ctx->d_lut.as<float>();
     P.prims_flat = ctx->d_prims_flat.as<DPrimFlat>(); P.prims_box = ctx->d_prims_box.as<DPrimBox>(); // null where the table is empty
+    P.normals = ctx->d_normals.as<DSmooth>();
     const drmlt_camera &cam = scene->camera;
 
     ctx->film_floats = (size_t) cam.width * cam.height * 3;

@@ -533,8 +533,11 @@ template <int RULE> DEV V4Layout<RULE> v4_layout(const DParams &P, uint32_t qcap
 // it by scene_has_one_light(P) (device_types.h), again without a Build enumerator. stats[15] counts the waves that ran a one-light build.
 #define V4_ORBITAL_BUILD 16
 #define V4_ONE_LIGHT_BUILD 32
+// The F7 builds (flat scenes with spheres, point lights, the environment or vertex normals) are compiled for three waves per SIMD:
+// 165 to 168 registers, no scratch (tests/test_kernel_resources_smooth.py pins the counts). Every other build keeps the default bound.
+#define V4_MIN_WAVES(BUILD) ((((BUILD) & (V4_ORBITAL_BUILD - 1)) == 7) ? 3 : 1)
 template <int BUILD, bool LDS_TABLES, bool STAMPS, bool STACK16 = false, bool OVF = false>
-__global__ void __launch_bounds__(CHAIN_BLOCK) k_mutate_v4(DParams P, uint32_t n_mut, uint32_t mut_base) {
+__global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(DParams P, uint32_t n_mut, uint32_t mut_base) {
     constexpr int FEAT = BUILD & (V4_ORBITAL_BUILD - 1), RULE = (BUILD & V4_ORBITAL_BUILD) / V4_ORBITAL_BUILD;
     constexpr bool ONE_LIGHT = (BUILD & V4_ONE_LIGHT_BUILD) != 0;
     static_assert(!ONE_LIGHT || (FEAT == 0 && LDS_TABLES), "the one-light twins are those of the straight-line step");

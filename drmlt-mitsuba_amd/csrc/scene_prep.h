@@ -13,6 +13,7 @@
 #include <array>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -26,6 +27,7 @@ struct PreparedScene {
     std::vector<DBvh4Node> bvh;     // empty: brute force
     std::vector<DPrimFlat> flat;    // n_flat_rec records + two sentinels; empty: no flat loop (BVH, DRMLT_NO_FLAT_LOOP)
     std::vector<DPrimBox> boxes;    // n_box records + one sentinel; empty: no cuboids
+    std::vector<DSmooth> normals;   // one entry per smooth triangle, in shape order (its shading record holds the index); empty: none
     std::array<float, 32> lut{};    // reconstruction filter table
     DParams P{};
     int bvh_depth = 0;
@@ -123,6 +125,23 @@ inline std::string validate_emitters(const drmlt_scene &s, int technique) {
     return "";
 }
 
+// Vertex normals (drmlt_shape.normals, drmlt_scene.normals): triangles only, technique=path only. Returns "" or an error.
+inline std::string validate_normals(const drmlt_scene &s, int technique) {
+    if (s.n_normals < 0 || (s.n_normals > 0 && !s.normals)) return "vertex normals: n_normals must be >= 0 and normals non-null";
+    for (int i = 0; i < s.n_shapes && s.shapes; ++i) {
+        const drmlt_shape &in = s.shapes[i];
+        if (in.normals == 0) continue;
+        const std::string which = "shape " + std::to_string(i) + ": ";
+        if (in.type != DRMLT_SHAPE_TRIANGLE) return which + "vertex normals on a " + (in.type == DRMLT_SHAPE_RECTANGLE ? "rectangle" : in.type == DRMLT_SHAPE_SPHERE ? "sphere" : "shape that is no triangle") + " (only triangles carry them)";
+        if (in.normals < 0 || in.normals > s.n_normals) return which + "vertex-normal index " + std::to_string(in.normals) + " out of range (n_normals = " + std::to_string(s.n_normals) + "; 0 = face normal, k = entry k - 1)";
+        if (technique != DRMLT_TECH_PATH)
+            return which + "vertex normals are supported for technique=path only: bdpt and mmlt need the geometric normal beside the shading normal in every vertex record, and the adjoint correction of the light subpath's BSDFs";
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(s.normals[9 * (size_t) (in.normals - 1) + k])) return which + "vertex normal is not finite";
+    }
+    return "";
+}
+
 // Flatten the scene into intersection + shading records (out.prims in the caller's order, out.shade, out.bsdfs, out.emitters).
 // BSDF and emitter types: validate_bsdfs / validate_emitters have checked them. Returns "" or an error.
 inline std::string build_scene(const drmlt_scene &s, const Knobs &K, PreparedScene &out, std::vector<PrimBounds> &bounds, std::vector<QuadGeo> &geo) {
@@ -171,6 +190,15 @@ inline std::string build_scene(const drmlt_scene &s, const Knobs &K, PreparedSce
             for (int k = 0; k < 3; ++k) { sh.origin[k] = (float) p0[k]; sh.eu[k] = (float) e1[k]; sh.ev[k] = (float) e2[k]; sh.n[k] = (float) n[k]; }
             sh.inv_len_eu = (float) (1.0 / std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]));
             sh.inv_area = (float) (1.0 / (0.5 * len));
+            if (in.normals > 0) { // validate_normals has checked the index: the shading record alone knows (kind PRIM_SMOOTH, below)
+                const float *vn = s.normals + 9 * (size_t) (in.normals - 1);
+                DSmooth e{};
+                for (int k = 0; k < 3; ++k) { e.n0[k] = vn[k]; e.d1[k] = vn[3 + k] - vn[k]; e.d2[k] = vn[6 + k] - vn[k]; }
+                const uint32_t index = (uint32_t) out.normals.size() + SMOOTH_INDEX_BIAS; // a normal float's bits (smooth_frame.h)
+                sh.n[1] = sh.n[2] = 0.f;
+                memcpy(&sh.n[0], &index, sizeof index); // where a flat primitive has its normal (device_types.h: PRIM_SMOOTH)
+                out.normals.push_back(e);
+            }
             for (int k = 0; k < 3; ++k) {
                 double a = p0[k], b = p0[k] + e1[k], c = p0[k] + e2[k];
                 pb.lo[k] = (float) std::min(a, std::min(b, c)); pb.hi[k] = (float) std::max(a, std::max(b, c));
@@ -214,7 +242,7 @@ inline std::string build_scene(const drmlt_scene &s, const Knobs &K, PreparedSce
             return "unknown shape type " + std::to_string(in.type);
         }
         for (int k = 0; k < 12; ++k) g.m[k] = (float) inv[k];
-        sh.bsdf |= g.type << 24;
+        sh.bsdf |= (in.type == DRMLT_SHAPE_TRIANGLE && in.normals > 0 ? PRIM_SMOOTH : g.type) << 24;
         g.shade = (int32_t) out.shade.size();
         out.prims.push_back(g);
         out.shade.push_back(sh);
@@ -231,7 +259,8 @@ inline std::string build_scene(const drmlt_scene &s, const Knobs &K, PreparedSce
         for (size_t i = 0; i < out.prims.size(); ++i) {
             bool did = false;
             if (i + 1 < out.prims.size() && s.shapes[i].type == DRMLT_SHAPE_TRIANGLE && s.shapes[i + 1].type == DRMLT_SHAPE_TRIANGLE &&
-                s.shapes[i].bsdf == s.shapes[i + 1].bsdf && s.shapes[i].emitter < 0 && s.shapes[i + 1].emitter < 0) {
+                s.shapes[i].bsdf == s.shapes[i + 1].bsdf && s.shapes[i].emitter < 0 && s.shapes[i + 1].emitter < 0 &&
+                s.shapes[i].normals == 0 && s.shapes[i + 1].normals == 0) { // (smooth triangles stay single: no pair, so no cuboid face either)
                 const float *A = s.shapes[i].data, *B = s.shapes[i + 1].data; // A: a,b,c   B: a',c',d
                 bool shared = true;
                 for (int k = 0; k < 3; ++k) shared = shared && A[k] == B[k] && A[6 + k] == B[3 + k];
@@ -356,6 +385,7 @@ inline std::string prepare_scene(const drmlt_config &cfg, const drmlt_scene &sce
     out = PreparedScene();
     std::string e = validate_bsdfs(scene);
     if (e.empty()) e = validate_emitters(scene, cfg.technique);
+    if (e.empty()) e = validate_normals(scene, cfg.technique);
     if (!e.empty()) return e;
     const drmlt_camera &cam = scene.camera;
     if (cam.width <= 0 || cam.height <= 0) return "film size must be positive";
@@ -366,6 +396,9 @@ inline std::string prepare_scene(const drmlt_config &cfg, const drmlt_scene &sce
     std::vector<QuadGeo> geo; // world-space parallelograms of the flat records (box_merge.h)
     e = build_scene(scene, K, out, bounds, geo);
     if (!e.empty()) return e;
+    // one table entry per smooth triangle; the kernels address it by 32-bit byte offsets, the records by a biased index (smooth_frame.h)
+    if ((uint64_t) out.normals.size() * sizeof(DSmooth) >= (1ull << 32) || out.normals.size() >= SMOOTH_INDEX_MAX - SMOOTH_INDEX_BIAS)
+        return "scene too large: the vertex-normal table (one entry per smooth triangle) must stay below 4 GiB";
 
     // ---- acceleration structure: brute force over wave-uniform records for tiny scenes, BVH otherwise
     DParams &P = out.P;
@@ -500,6 +533,7 @@ inline std::string prepare_scene(const drmlt_config &cfg, const drmlt_scene &sce
     if (!out.emitters.empty()) { P.light = out.emitters[0]; P.light_shade = out.shade[(size_t) out.emitters[0].prim]; }
     for (const DBsdf &b : out.bsdfs) P.features |= b.type == DRMLT_BSDF_ROUGHCONDUCTOR ? 1 : ((b.type == DRMLT_BSDF_DIELECTRIC || b.type == DRMLT_BSDF_CONDUCTOR) ? 2 : 0);
     for (const DPrim &g : out.prims) if (g.type == PRIM_SPHERE) P.features |= 4;
+    if (!out.normals.empty()) P.features |= 4; // not a flat polygon
     P.env_emitter = -1;
     for (int i = 0; i < scene.n_emitters; ++i) {
         if (scene.emitters[i].type == DRMLT_EMITTER_POINT) P.features |= 4; // what is not a polygon

@@ -53,13 +53,16 @@ private:
 };
 
 // Flat scene as written by SceneData.save() (drmlt-mitsuba_amd/scenes.py): the arrays of drmlt_scene. The point lights'
-// positions, if the scene has any, follow the camera as a trailing block: "PNTS", a count, xyz floats per light.
+// positions, if the scene has any, follow the camera as a trailing block: "PNTS", a count, xyz floats per light. The vertex
+// normals of its smooth triangles (drmlt_scene.normals), if any, follow as a block "NRMS", a count, nine floats per entry.
 struct SceneFile {
     static constexpr uint32_t POINTS_TAG = 0x53544E50u; /* "PNTS" */
+    static constexpr uint32_t NORMALS_TAG = 0x534D524Eu; /* "NRMS" */
     std::vector<drmlt_shape> shapes;
     std::vector<drmlt_bsdf> bsdfs;
     std::vector<drmlt_emitter> emitters;
     std::vector<float> points;
+    std::vector<float> normals;
     drmlt_camera camera{};
     drmlt_scene view() const {
         drmlt_scene s;
@@ -70,6 +73,7 @@ struct SceneFile {
         s.n_emitters = (int32_t) emitters.size(); s.emitters = emitters.data();
         s.camera = camera;
         s.n_points = (int32_t) (points.size() / 3); s.points = points.empty() ? nullptr : points.data();
+        s.n_normals = (int32_t) (normals.size() / 9); s.normals = normals.empty() ? nullptr : normals.data();
         return s;
     }
     static SceneFile load(const std::string &path) {
@@ -87,11 +91,15 @@ struct SceneFile {
                  fread(&sf.camera, sizeof sf.camera, 1, f) == 1;
         }
         uint32_t blk[2];
-        if (ok && fread(blk, sizeof blk, 1, f) == 1) { // optional point-light block; a file without it ends at the camera
-            ok = blk[0] == POINTS_TAG && blk[1] <= (1u << 24);
+        bool seen_points = false, seen_normals = false;
+        while (ok && fread(blk, sizeof blk, 1, f) == 1) { // optional tagged blocks, points before normals; a file without them ends at the camera
+            const bool pts = blk[0] == POINTS_TAG && !seen_points && !seen_normals, nrm = blk[0] == NORMALS_TAG && !seen_normals;
+            ok = (pts || nrm) && blk[1] <= (1u << 24);
             if (ok) {
-                sf.points.resize((size_t) blk[1] * 3);
-                ok = fread(sf.points.data(), sizeof(float), sf.points.size(), f) == sf.points.size();
+                std::vector<float> &dst = pts ? sf.points : sf.normals;
+                (pts ? seen_points : seen_normals) = true;
+                dst.resize((size_t) blk[1] * (pts ? 3 : 9));
+                ok = fread(dst.data(), sizeof(float), dst.size(), f) == dst.size();
             }
         }
         fclose(f);

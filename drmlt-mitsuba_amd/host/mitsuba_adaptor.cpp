@@ -136,9 +136,10 @@ public:
         std::vector<drmlt_shape> shapes;
         std::vector<drmlt_bsdf> bsdfs;
         std::vector<drmlt_emitter> emitters;
+        std::vector<float> normals; // nine per smooth triangle (drmlt_scene.normals)
         const ref_vector<Shape> &mtsShapes = scene->getShapes();
         for (size_t i = 0; i < mtsShapes.size(); ++i)
-            appendShape(mtsShapes[i].get(), shapes, bsdfs, emitters);
+            appendShape(mtsShapes[i].get(), shapes, bsdfs, emitters, normals);
 
         drmlt_scene sc;
         memset(&sc, 0, sizeof sc);
@@ -146,6 +147,7 @@ public:
         sc.n_shapes = (int32_t) shapes.size(); sc.shapes = shapes.data();
         sc.n_bsdfs = (int32_t) bsdfs.size(); sc.bsdfs = bsdfs.data();
         sc.n_emitters = (int32_t) emitters.size(); sc.emitters = emitters.data();
+        sc.n_normals = (int32_t) (normals.size() / 9); sc.normals = normals.empty() ? NULL : normals.data();
         const PerspectiveCamera *cam = dynamic_cast<const PerspectiveCamera *>(sensor.get());
         if (!cam || cam->needsApertureSample())
             Log(EError, "The MI355X drmlt backend supports the `perspective` sensor only");
@@ -343,7 +345,7 @@ private:
     }
 
     void appendShape(const Shape *shape, std::vector<drmlt_shape> &shapes, std::vector<drmlt_bsdf> &bsdfs,
-                     std::vector<drmlt_emitter> &emitters) {
+                     std::vector<drmlt_emitter> &emitters, std::vector<float> &normals) {
         std::string name = shape->getClass()->getName();
         int bsdf = bsdfIndex(shape->getBSDF(), bsdfs);
         size_t first = shapes.size();
@@ -367,8 +369,14 @@ private:
             shapes.push_back(s);
         } else if (shape->getClass()->derivesFrom(MTS_CLASS(TriMesh))) {
             const TriMesh *mesh = static_cast<const TriMesh *>(shape);
-            if (mesh->getVertexNormals() != NULL && !shape->getProperties().getBoolean("faceNormals", false))
+            // Vertex normals (absent under faceNormals=true, trimesh.cpp:66-77) are handed through per triangle under technique=path,
+            // as stored: the device interpolates them as skdtree.h:355-396 does. bdpt / mmlt have no shading normals on the device
+            // (they would need the geometric normal in every vertex record): face normals, and the warning, as before.
+            const Normal *vn = shape->getProperties().getBoolean("faceNormals", false) ? NULL : mesh->getVertexNormals();
+            if (vn != NULL && m_cfg.technique != DRMLT_TECH_PATH) {
                 Log(EWarn, "Mesh \"%s\": smooth vertex normals are ignored (face normals are used)", mesh->getName().c_str());
+                vn = NULL;
+            }
             const Triangle *tri = mesh->getTriangles();
             const Point *pos = mesh->getVertexPositions();
             s.type = DRMLT_SHAPE_TRIANGLE;
@@ -382,6 +390,13 @@ private:
                 const double e1[3] = {q[1][0] - q[0][0], q[1][1] - q[0][1], q[1][2] - q[0][2]}, e2[3] = {q[2][0] - q[0][0], q[2][1] - q[0][1], q[2][2] - q[0][2]};
                 const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
                 areas.push_back(0.5 * std::sqrt(cx * cx + cy * cy + cz * cz));
+                if (vn != NULL) {
+                    for (int v = 0; v < 3; ++v) {
+                        const Normal &nv = vn[tri[i].idx[v]];
+                        normals.push_back((float) nv.x); normals.push_back((float) nv.y); normals.push_back((float) nv.z);
+                    }
+                    s.normals = (int32_t) (normals.size() / 9);
+                }
                 shapes.push_back(s);
             }
         } else {

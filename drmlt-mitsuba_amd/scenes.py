@@ -54,6 +54,7 @@ def lookat(origin, target, up):
 
 
 POINTS_TAG = 0x53544E50  # "PNTS": the point-light block of a scene file (SceneData.save)
+NORMALS_TAG = 0x534D524E  # "NRMS": the vertex-normal block
 
 
 class SceneData:
@@ -61,6 +62,7 @@ class SceneData:
         self.name = name
         self.shapes, self.bsdfs, self.emitters = [], [], []
         self.points = []   # positions of the point lights (drmlt_scene.points)
+        self.normals = []  # vertex normals of the smooth triangles, nine floats each (drmlt_scene.normals)
         self.camera = abi.Camera()
         self._keep = None
 
@@ -124,12 +126,18 @@ class SceneData:
         self.shapes.append(s)
         return len(self.shapes) - 1
 
-    def triangle(self, p0, p1, p2, bsdf, radiance=None):
+    def triangle(self, p0, p1, p2, bsdf, radiance=None, normals=None):
+        """normals: the three vertex normals (at p0, p1, p2) of a smooth-shaded triangle, handed on as they are -- Mitsuba
+        interpolates them as stored and normalises only the sum (skdtree.h:355-396). None: the face normal. technique=path only."""
         s = abi.Shape()
         s.type = abi.SHAPE_TRIANGLE
         s.bsdf = bsdf
         s.emitter = self._emit(radiance) if radiance is not None else -1
         s.data[:9] = list(p0) + list(p1) + list(p2)
+        if normals is not None:
+            vn = np.asarray(normals, dtype=np.float64).reshape(9)
+            self.normals.append(tuple(float(v) for v in vn))
+            s.normals = len(self.normals)
         self.shapes.append(s)
         return len(self.shapes) - 1
 
@@ -186,7 +194,8 @@ class SceneData:
     def save(self, path):
         """Flat binary scene file read by the C++ host (host/drmlt_integrator.hpp: SceneFile::load). Point lights follow the
         camera as a trailing block ("PNTS", count, xyz float32 each), written only when there are any: a scene without them
-        gives the same bytes as before the block existed."""
+        gives the same bytes as before the block existed. The vertex normals follow in the same way ("NRMS", count, nine float32
+        each), only when there are any."""
         import struct as _st
         with open(path, "wb") as f:
             f.write(_st.pack("<8I", 0x4C4D5244, abi.ABI_VERSION, len(self.shapes), len(self.bsdfs), len(self.emitters),
@@ -198,6 +207,9 @@ class SceneData:
             if self.points:
                 f.write(_st.pack("<2I", POINTS_TAG, len(self.points)))
                 f.write(np.asarray(self.points, dtype="<f4").tobytes())
+            if self.normals:
+                f.write(_st.pack("<2I", NORMALS_TAG, len(self.normals)))
+                f.write(np.asarray(self.normals, dtype="<f4").tobytes())
 
     def struct(self):
         sh = (abi.Shape * len(self.shapes))(*self.shapes)
@@ -213,7 +225,10 @@ class SceneData:
         pts = (C.c_float * max(3, 3 * len(self.points)))(*[v for p in self.points for v in p])
         s.n_points = len(self.points)
         s.points = C.cast(pts, C.POINTER(C.c_float))
-        self._keep = (sh, bs, em, pts)
+        nrm = (C.c_float * max(9, 9 * len(self.normals)))(*[v for n in self.normals for v in n])
+        s.n_normals = len(self.normals)
+        s.normals = C.cast(nrm, C.POINTER(C.c_float))
+        self._keep = (sh, bs, em, pts, nrm)
         return s
 
 
@@ -309,9 +324,11 @@ def mirror_room(res=256):
     return sd
 
 
-def triangle_soup(n_tris=2000, res=128, seed=7):
-    """Closed room filled with small random diffuse triangles: a scene large enough that the BVH matters."""
+def triangle_soup(n_tris=2000, res=128, seed=7, smooth=False):
+    """Closed room filled with small random diffuse triangles: a scene large enough that the BVH matters. smooth: every triangle
+    carries vertex normals, each jittered about the face normal (by less than 44 degrees, unnormalised); the geometry is the same."""
     rng = np.random.default_rng(seed)
+    nrng = np.random.default_rng([seed, 1])   # the normals' own stream: the triangles do not depend on the flag
     sd = SceneData("soup_%d" % n_tris)
     white = sd.diffuse(0.7)
     red = sd.diffuse(0.63, 0.065, 0.05)
@@ -324,9 +341,60 @@ def triangle_soup(n_tris=2000, res=128, seed=7):
         c[1] = rng.uniform(-0.95, 0.5)
         e1 = rng.normal(size=3) * 0.06
         e2 = rng.normal(size=3) * 0.06
-        sd.triangle(c, c + e1, c + e2, mats[i % 3])
+        vn = None
+        if smooth:
+            fn = np.cross(e1, e2)
+            fn /= np.linalg.norm(fn)
+            vn = (fn + nrng.uniform(-0.4, 0.4, (3, 3))) * nrng.uniform(0.5, 2.0, (3, 1))
+        sd.triangle(c, c + e1, c + e2, mats[i % 3], normals=vn)
     sd.rectangle(translate(0, 0.995, 0) @ rotate("x", 90) @ scale(0.3), black, radiance=20.0)
     sd.set_camera(lookat((0, 0, 3.9), (0, 0, 0), (0, 1, 0)), 39.3077, res, res, abi.FILTER_BOX, 0.5)
+    return sd
+
+
+def icosphere(level=1):
+    """Unit icosphere: (vertices [n, 3], faces [m, 3]) after `level` subdivisions (20 * 4^level faces), outward winding. On the
+    unit sphere a vertex is its own radial normal."""
+    g = (1.0 + math.sqrt(5.0)) / 2.0
+    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g),
+         (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    verts = [np.asarray(p, dtype=np.float64) / math.sqrt(1.0 + g * g) for p in v]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+             (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(level):
+        mid, out = {}, []
+
+        def midpoint(a, b):
+            key = (min(a, b), max(a, b))
+            if key not in mid:
+                m = verts[a] + verts[b]
+                verts.append(m / np.linalg.norm(m))
+                mid[key] = len(verts) - 1
+            return mid[key]
+        for a, b, c in faces:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            out += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = out
+    return np.asarray(verts), np.asarray(faces, dtype=np.int64)
+
+
+def smooth_room(res=64, level=1, smooth=True):
+    """mirror_room's closed room with a diffuse floor and an icosphere (20 * 4^level triangles, radius 0.35) standing on it,
+    shaded with its radial vertex normals. smooth=False: the faceted twin, the same triangles with face normals."""
+    sd = SceneData("smooth_room" if smooth else "faceted_room")
+    white = sd.diffuse(0.725, 0.71, 0.68)
+    red = sd.diffuse(0.63, 0.065, 0.05)
+    green = sd.diffuse(0.14, 0.45, 0.091)
+    black = sd.diffuse(0.0)
+    _room(sd, white, red, green)
+    sd.rectangle(translate(0, 0, 1) @ rotate("y", 180), white)                        # front wall (room is closed)
+    verts, faces = icosphere(level)
+    centre, radius = np.array([0.0, -0.65, -0.4]), 0.35
+    for a, b, c in faces:
+        vn = (verts[a], verts[b], verts[c]) if smooth else None
+        sd.triangle(centre + radius * verts[a], centre + radius * verts[b], centre + radius * verts[c], white, normals=vn)
+    sd.rectangle(translate(0, 0.995, -0.2) @ rotate("x", 90) @ scale(0.25), black, radiance=(17.0, 12.0, 4.0))
+    sd.set_camera(lookat((0, -0.2, 0.95), (0, -0.3, -0.4), (0, 1, 0)), 70.0, res, res, abi.FILTER_BOX, 0.5)
     return sd
 
 
@@ -399,4 +467,5 @@ def deep_chain(res=64, n=160):
 
 
 SCENES = {"cornell_c1": cornell_c1, "cornell_c2": cornell_c2, "glass_sphere": glass_sphere, "door_c3": door_c3, "mirror_room": mirror_room,
-          "triangle_soup": triangle_soup, "caustic_c5": caustic_c5, "cornell_point": cornell_point, "cornell_sky": cornell_sky}
+          "triangle_soup": triangle_soup, "caustic_c5": caustic_c5, "cornell_point": cornell_point, "cornell_sky": cornell_sky,
+          "smooth_room": smooth_room}

@@ -138,6 +138,9 @@ typedef struct drmlt_config {
 
 /* One primitive. `data` by type:
  *   TRIANGLE   p0.xyz p1.xyz p2.xyz            (face normal = (p1-p0)x(p2-p0))
+ *              `normals` = k >= 1: the triangle is shaded with the vertex normals of entry k-1 of drmlt_scene.normals,
+ *              interpolated as TriMesh does (include/mitsuba/render/skdtree.h:355-396: normalize(n0 (1-u-v) + n1 u + n2 v)
+ *              of the normals AS STORED, frame by computeShadingFrame with dpdu = p1 - p0); technique=path only.
  *   RECTANGLE  row-major 3x4 objectToWorld of Mitsuba's rectangle
  *              (local [-1,1]^2 in the z=0 plane, normal +z; rectangle.cpp:80-112)
  *   SPHERE     center.xyz radius
@@ -146,7 +149,7 @@ typedef struct drmlt_shape {
     int32_t type;
     int32_t bsdf;        /* index into bsdfs                         */
     int32_t emitter;     /* index into emitters, or -1               */
-    int32_t reserved;
+    int32_t normals;     /* 0: the face normal; k >= 1: entry k-1 of drmlt_scene.normals (triangles only) */
     float   data[12];
 } drmlt_shape;
 
@@ -192,8 +195,11 @@ typedef struct drmlt_camera {
     float   filter_param;   /* box: radius (0.5); gaussian: stddev (0.5)      */
 } drmlt_camera;
 
-/* struct_size: sizeof(drmlt_scene), or DRMLT_SCENE_SIZE_NO_POINTS -- the layout that ends at `camera` (callers
- * built before the point-light fields), which means "no point lights": the trailing fields are then not read. */
+/* struct_size: sizeof(drmlt_scene), or one of the two older layouts:
+ *   DRMLT_SCENE_SIZE_NO_NORMALS  ends at `points` (callers built before the vertex normals): no triangle is smooth, and
+ *                                drmlt_shape.normals -- `reserved` to those callers -- is not read;
+ *   DRMLT_SCENE_SIZE_NO_POINTS   ends at `camera` (callers built before the point-light fields): that, and no point lights.
+ * The trailing fields an older layout lacks are not read. */
 typedef struct drmlt_scene {
     uint32_t struct_size;       /* = sizeof(drmlt_scene) */
     int32_t  n_shapes;
@@ -205,11 +211,15 @@ typedef struct drmlt_scene {
     drmlt_camera camera;
     int32_t  n_points;          /* positions of the POINT emitters           */
     const float *points;        /* xyz per point light (3 * n_points floats) */
+    int32_t  n_normals;         /* entries of `normals`                      */
+    const float *normals;       /* nine floats per entry: the normals at p0, p1, p2 of the triangles that name it */
 } drmlt_scene;
 
 /* sizeof(drmlt_scene) up to and including `camera`, padded to the struct's alignment */
 #define DRMLT_SCENE_SIZE_NO_POINTS \
     ((offsetof(drmlt_scene, camera) + sizeof(drmlt_camera) + sizeof(void *) - 1) / sizeof(void *) * sizeof(void *))
+/* sizeof(drmlt_scene) up to and including `points` */
+#define DRMLT_SCENE_SIZE_NO_NORMALS (offsetof(drmlt_scene, points) + sizeof(const float *))
 
 /* ---- statistics: numerators / denominators of drmlt_proc.cpp:34-49 ----- */
 
