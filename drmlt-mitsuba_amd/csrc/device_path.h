@@ -685,6 +685,20 @@ struct OneLightTables {
     DEV DShade emitter_shade(int, const DEmitter &) const { DShade s = P.light_shade; asm volatile("" : "+s"(s.inv_area)); return s; }
     DEV constexpr int n_emitters(const DParams &) const { return 1; }
 };
+// OneLightTables with the light's two records held by the caller, in vector registers across its loop (k_mutate_w2, compiled for two
+// waves per SIMD, has them to spare): no scalar load at the head of the step. The shape tag steers a wave-uniform branch of the
+// step and goes back to a scalar register (one v_readfirstlane); everything else is a VALU operand.
+struct HeldLightTables {
+    LdsTables L;
+    const DEmitter &E;
+    const DShade &S;
+    DEV DShade shade(int i) const { return L.shade(i); }
+    DEV DBsdf bsdf(int i) const { return L.bsdf(i); }
+    DEV DEmitter emitter(int) const { return E; }
+    DEV float emitter_cdf_lo(int) const { return E.cdf_lo; }
+    DEV DShade emitter_shade(int, const DEmitter &) const { DShade s = S; s.bsdf = __builtin_amdgcn_readfirstlane(s.bsdf); return s; }
+    DEV constexpr int n_emitters(const DParams &) const { return 1; }
+};
 // BSDF and emitter records in LDS, shading records in device memory: for kernels whose own rows leave less LDS than the shading table
 // needs (k_mutate_bdpt at two waves per SIMD: 19.25 KB of rows; the Cornell scene's 30 shading records are 1.9 KB, its four BSDFs and one
 // emitter 224 bytes)

@@ -349,6 +349,16 @@ template <int RULE = RULE_GENERIC> struct RowSamplerT {
     }
 };
 typedef RowSamplerT<> RowSampler;
+// RowSamplerT::fill_first with the block's uniforms drawn by the CALLER (k_mutate_w2: one Philox site serves proposal and coin
+// items alike, and only this tail differs): the same reads, the same first_stage_block, the same writes.
+template <int RULE> DEV void row_fill_first_drawn(const RowSamplerT<RULE> &s, uint32_t b, const Unit4 &u, bool large) {
+    const float *xs = &lds_x[s.x_off + 4u * b * s.stride];
+    float *ys = &lds_x[s.y_off + 4u * b * s.stride];
+    const float x4[4] = {wrap01(xs[0]), wrap01(xs[s.stride]), wrap01(xs[2u * s.stride]), wrap01(xs[3u * s.stride])};
+    float y[4];
+    first_stage_block(RowSamplerT<RULE>::orbital ? 2 : s.type, large, u, x4, y);
+    ys[0] = y[0]; ys[s.stride] = y[1]; ys[2u * s.stride] = y[2]; ys[3u * s.stride] = y[3];
+}
 
 // ------------------------------------------------------------------ PSS sampler of k_mutate_v5
 // Where a wave's proposal rows live. RowsLds: 64 columns of lds_x (one per chain of the wave). RowsMem: device memory, [dim][chain]

@@ -890,6 +890,352 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(
 }
 
 // ------------------------------------------------------------------------------------------
+// k_mutate_w2: k_mutate_v4<V4_ONE_LIGHT_BUILD | V4_ORBITAL_BUILD, true, false> -- flat scene, tables in LDS, orbital rule, one area
+// light -- compiled for TWO waves per SIMD. launch_mutate runs it in place of that twin on launches that cannot have a third
+// wave on a SIMD (launch_plan.h: w2_launch), bench.py's flagship line among them: there the twin's 168-register bound buys
+// nothing, and a wave's rate is its own serial time, instructions plus the waits one partner cannot cover. A kernel of its own
+// name because the v3 / v4 / v5 instantiations are pinned register by register (tests/test_kernel_resources_smooth.py).
+// Same chains bit for bit: the LDS layout, the run-ahead protocol, the splat queue, the prologue and epilogue are k_mutate_v4's,
+// every floating-point expression is a header routine it shares with the twin. What differs (DESIGN.md section 7a has the
+// measurements; each can be compiled out for an A/B run):
+//   -DW2_NO_HELD_CONSTANTS  off: the wave-uniform constants that are only ever VALU operands or LDS address terms -- layout offsets,
+//                           the light's two records, the camera, p_large, the roulette depths -- are read ONCE, in the prologue,
+//                           and stay in vector registers (W2Held); the step and the bookkeeping branch open without a scalar load
+//                           or v4_layout. The step's wait chain is otherwise the twin's: five component reads, a wait, the hit's
+//                           shading record, a wait, the BSDF record.
+//   -DW2_SCALARS_LOADED     off: what the bookkeeping branch needs in SCALAR registers (the importance map, chain_done, waves_left,
+//                           the Philox keys, chain_offset, eff_dim, timid_after_large) waits in vector registers too and comes
+//                           back with one v_readfirstlane each: thirteen VALU instructions for a scalar-cache round trip. The ray
+//                           pass reads its record pointers and counts as k_mutate_v4 does (holding them measured slower).
+//   -DW2_TWO_PHILOX         off: a fill item computes its counter and tag per lane and calls Philox ONCE; only the tail differs
+//                           (row_fill_first_drawn for a proposal block, four writes for a coin block).
+// Not here: the step's component reads issued ahead of the ray pass, and components and shading record requested in one batch
+// (both built and measured: no gain and a loss, section 7a). The splat path keeps
+// film_put_channel's debug test (DRMLT_DEBUG bit 1 must go on working; one scalar compare per flushed splat).
+// stats[16] counts the waves that ran it (no build without stamps writes that slot; drmlt_stats_get prints it under DRMLT_VERBOSE).
+template <class T> DEV void hold_v(T &x) { asm volatile("" : "+v"(x)); }
+DEV uint32_t wave_uniform(uint32_t v) { return (uint32_t) __builtin_amdgcn_readfirstlane((int) v); }
+template <class T> DEV T *uniform_ptr(uint32_t lo, uint32_t hi) { return reinterpret_cast<T *>((uintptr_t) wave_uniform(lo) | ((uintptr_t) wave_uniform(hi) << 32)); }
+
+struct W2Held {
+    uint32_t group, coin_off, list_off, q_off, qcap, shade_off, bsdf_off; // v4_layout
+    int eff_dim, rr_depth, max_depth;                                     // path_step_diffuse
+    int exclude_direct, width, height;                                    // path_init, path_begin
+    float tan_half_fov, inv_aspect, near_clip, far_clip, cam[12];
+    float p_large;
+    DEmitter light;
+    DShade light_shade;
+};
+DEV W2Held w2_held(const DParams &P) {
+    const V4Layout<RULE_ORBITAL> Y = v4_layout<RULE_ORBITAL>(P, V4_QCAP);
+    W2Held H;
+    H.group = Y.group; H.coin_off = Y.L.coin_off; H.list_off = Y.L.list_off; H.q_off = Y.L.q_off; H.qcap = Y.L.qcap;
+    H.shade_off = Y.LT.shade_off; H.bsdf_off = Y.LT.bsdf_off;
+    H.eff_dim = P.eff_dim; H.rr_depth = P.rr_depth; H.max_depth = P.max_depth;
+    H.exclude_direct = P.exclude_direct; H.width = P.width; H.height = P.height;
+    H.tan_half_fov = P.tan_half_fov; H.inv_aspect = P.inv_aspect; H.near_clip = P.near_clip; H.far_clip = P.far_clip;
+#pragma unroll
+    for (int i = 0; i < 12; ++i) H.cam[i] = P.cam[i];
+    H.p_large = P.p_large;
+    H.light = P.light; H.light_shade = P.light_shade;
+    return H;
+}
+// pin what the loop reads of it in vector registers: an opaque definition the compiler cannot rematerialise as a scalar load
+DEV void w2_hold(W2Held &H) {
+    hold_v(H.group); hold_v(H.coin_off); hold_v(H.list_off); hold_v(H.q_off); hold_v(H.qcap); hold_v(H.shade_off); hold_v(H.bsdf_off);
+    hold_v(H.eff_dim); hold_v(H.rr_depth); hold_v(H.max_depth); hold_v(H.exclude_direct); hold_v(H.width); hold_v(H.height);
+    hold_v(H.tan_half_fov); hold_v(H.inv_aspect); hold_v(H.near_clip); hold_v(H.far_clip); hold_v(H.p_large);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) hold_v(H.cam[i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        hold_v(H.light.radiance[i]); hold_v(H.light_shade.origin[i]); hold_v(H.light_shade.eu[i]); hold_v(H.light_shade.ev[i]); hold_v(H.light_shade.n[i]);
+    }
+    hold_v(H.light.cdf_lo); hold_v(H.light.cdf_hi); hold_v(H.light_shade.inv_area); hold_v(H.light_shade.bsdf);
+}
+DEV RowSamplerT<RULE_ORBITAL> w2_sampler(uint32_t key0, uint32_t key1) { // the uniform fields, as v4_layout sets them under the orbital rule
+    RowSamplerT<RULE_ORBITAL> s;
+    s.key0 = key0; s.key1 = key1;
+    s.mode = SM_STAGE1; s.type = 2; s.sigma2 = 0.f;
+    s.stride = V4_STRIDE;
+    s.x_off = s.y_off = s.xyz = 0u;
+    return s;
+}
+#if defined(W2_NO_HELD_CONSTANTS) && !defined(W2_SCALARS_LOADED)
+#define W2_SCALARS_LOADED // (the scalars' vector copies sit beside W2Held)
+#endif
+#ifndef W2_NO_HELD_CONSTANTS
+#define W2_SECTION(name) const W2Held &name = held
+#else
+#define W2_SECTION(name) SECTION_PARAMS(name##_p); const W2Held name = w2_held(name##_p)
+#endif
+
+__global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_t n_mut, uint32_t mut_base) {
+    typedef RowSamplerT<RULE_ORBITAL> RowSampler;
+    if (threadIdx.x == 0) { atomicAdd(P.stats + 14, 1ull); atomicAdd(P.stats + 15, 1ull); atomicAdd(P.stats + 16, 1ull); }
+    const uint32_t lane = threadIdx.x;
+    const uint32_t sub = lane & 31u;
+    const bool helper = lane >= 32u;
+    const uint32_t c = blockIdx.x * 32u + sub;
+    const bool live = !helper && c < P.n_chains;
+    const uint32_t cc = c < P.n_chains ? c : P.n_chains - 1;
+    const uint32_t S = V4_STRIDE;
+    int smp_mode = SM_STAGE1;
+    uint32_t roles;
+    uint32_t qn = 0u;
+    ChainState cs;
+    float cum = 0.f;
+    Counters ct = {0u, 0u, 0u, 0u, 0u};
+    PathState ps;
+    bool helper_has_ray = false;
+    Hit h{-1, 0.f, 0.f, 0.f};
+    int batch;
+    uint32_t base = 0u, target = 0u, limit = 0u;
+    bool reported = false;
+#ifndef W2_NO_HELD_CONSTANTS
+    W2Held held = w2_held(P);
+    w2_hold(held);
+#endif
+#ifndef W2_SCALARS_LOADED
+    // (W2Held's companions: what the bookkeeping branch needs in SCALAR registers, one v_readfirstlane each where it opens)
+    uint32_t imp_lo = (uint32_t) (uintptr_t) P.importance, imp_hi = (uint32_t) ((uintptr_t) P.importance >> 32);
+    uint32_t done_lo = (uint32_t) (uintptr_t) P.chain_done, done_hi = (uint32_t) ((uintptr_t) P.chain_done >> 32);
+    uint32_t left_lo = (uint32_t) (uintptr_t) P.waves_left, left_hi = (uint32_t) ((uintptr_t) P.waves_left >> 32);
+    uint32_t key0_v = P.key0, key1_v = P.key1, chain_off_v = P.chain_offset, timid_v = (uint32_t) P.timid_after_large;
+    hold_v(imp_lo); hold_v(imp_hi); hold_v(done_lo); hold_v(done_hi); hold_v(left_lo); hold_v(left_hi);
+    hold_v(key0_v); hold_v(key1_v); hold_v(chain_off_v); hold_v(timid_v);
+#endif
+    { // the prologue of k_mutate_v4
+        const V4Layout<RULE_ORBITAL> Y = v4_layout<RULE_ORBITAL>(P, V4_QCAP);
+        roles = RowSampler::first_roles(Y.group, sub);
+        if (!helper) {
+            for (uint32_t k = 0; k < Y.D; ++k) lds_x[k * S + sub] = unwrap01(P.x[(size_t) k * P.n_chains + cc]);
+            for (uint32_t k = Y.D; k < Y.D4; ++k) lds_x[k * S + sub] = 0.f;
+        }
+        cs.cur.lum = P.cur_lum[cc]; cs.cur.px = P.cur_px[cc]; cs.cur.py = P.cur_py[cc];
+        cs.cur.r = P.cur_r[cc]; cs.cur.g = P.cur_g[cc]; cs.cur.b = P.cur_b[cc];
+        cs.y = cs.cur; cs.z = cs.cur;
+        cs.a1 = 0.f; cs.coin_acc1 = cs.coin_acc2 = cs.coin_mix = 0.f;
+        cs.it = 0u; cs.nd1 = cs.nd2 = 0u; cs.stage = -1; cs.large = false;
+        path_init(P, ps);
+        base = (P.chain_done && live) ? P.chain_done[cc] : mut_base;
+        target = P.chain_done ? n_mut : mut_base + n_mut;
+        limit = P.chain_done ? P.run_limit : target;
+        ps.phase = (live && base < limit) ? PH_DONE : PH_IDLE;
+        ps.o = mk3(0.f, 0.f, 0.f); ps.d = mk3(0.f, 0.f, 1.f); ps.tmin = 0.f; ps.tmax = 0.f;
+        batch = P.mh_batch > 32 ? 32 : P.mh_batch;
+        stage_tables(P, Y.LT, lane);
+        if (!helper) {
+            const u4 coins = philox4x32_10(P.key0, P.key1, 0u, base, P.chain_offset + blockIdx.x * 32u + sub, TAG_COIN);
+            float *dst = &lds_x[Y.L.coin_off + sub];
+            dst[0] = u32_to_unit(coins.x); dst[S] = u32_to_unit(coins.y); dst[2u * S] = u32_to_unit(coins.z); dst[3u * S] = u32_to_unit(coins.w);
+        }
+    }
+
+    for (;;) {
+        const bool parked = ps.phase == PH_DONE;
+        const unsigned long long pmask = __ballot(parked);
+        const unsigned long long rmask = __ballot(ps.phase != PH_DONE && ps.phase != PH_IDLE);
+        if (!pmask && !rmask) break;
+        if (pmask && (__popcll(pmask) >= batch || !rmask)) {
+            // the branch's scalars: what steers wave-uniform branches, loop bounds and scalar addresses (importance, timid_after_large,
+            // eff_dim, chain_done, waves_left) and the Philox keys -- one block for the whole branch
+#ifndef W2_SCALARS_LOADED
+            DParams Pm{};
+            Pm.importance = uniform_ptr<const float>(imp_lo, imp_hi); Pm.width = (int) wave_uniform((uint32_t) held.width); Pm.height = (int) wave_uniform((uint32_t) held.height);
+            Pm.chain_done = uniform_ptr<uint32_t>(done_lo, done_hi); Pm.waves_left = uniform_ptr<uint32_t>(left_lo, left_hi);
+            Pm.key0 = wave_uniform(key0_v); Pm.key1 = wave_uniform(key1_v); Pm.chain_offset = wave_uniform(chain_off_v);
+            Pm.eff_dim = (int) wave_uniform((uint32_t) held.eff_dim); Pm.timid_after_large = (int) wave_uniform(timid_v);
+            Pm.use_mixture = 0; Pm.acceptance_map = 0; Pm.type = 2; // (the orbital rule: mh_decide<RULE_ORBITAL> reads none of them)
+#else
+            SECTION_PARAMS(Pm);
+#endif
+            W2_SECTION(C);
+            const V4Lds L{C.coin_off, C.list_off, C.q_off, C.qcap};
+            RowSampler smp = w2_sampler(Pm.key0, Pm.key1);
+            smp.set_roles(roles, C.group, sub); smp.mode = smp_mode;
+            const uint32_t D4 = ((uint32_t) Pm.eff_dim + 3u) & ~3u, nb1 = D4 / 4u;
+            int *const lds_list = reinterpret_cast<int *>(&lds_x[L.list_off]);
+            __builtin_amdgcn_s_setprio(2);
+            if (qn + 64u > wave_uniform(L.qcap)) { SECTION_PARAMS(Pf); v4_flush(Pf, L, qn, lane); }
+            // ---- decide (parked chain lanes), as k_mutate_v4: slot A = the current state when it is left, else y; slot B = y when
+            // z is adopted, else z
+            int commit = 0, kind = 0; // kind: 0 nothing / finished, 1 next mutation, 2 second stage
+            bool wantA = false, wantB = false;
+            float eAx = 0.f, eAy = 0.f, eAr = 0.f, eAg = 0.f, eAb = 0.f;
+            float eBx = 0.f, eBy = 0.f, eBr = 0.f, eBg = 0.f, eBb = 0.f;
+            if (parked) {
+                const MhDigest o = mh_decide<RULE_ORBITAL>(Pm, cs, smp, ps, ct);
+                if (o.decided) {
+                    cum += o.w.w0;
+                    const bool a1st = o.acc1, a2nd = o.acc2, adopt = a1st || a2nd;
+                    const DSplat sb = select_splat(a2nd, cs.y, cs.z);
+                    const float wb = a2nd ? o.w.w1 : o.w.w2;
+                    wantB = !a1st && wb > 0.f;
+                    eBx = sb.px; eBy = sb.py; eBr = sb.r * wb; eBg = sb.g * wb; eBb = sb.b * wb;
+                    const DSplat sa = select_splat(adopt, cs.cur, cs.y);
+                    const float wa = adopt ? cum : o.w.w1;
+                    wantA = wa > 0.f;
+                    eAx = sa.px; eAy = sa.py; eAr = sa.r * wa; eAg = sa.g * wa; eAb = sa.b * wa;
+                    if (adopt) {
+                        cum = a1st ? o.w.w1 : o.w.w2;
+                        cs.cur = select_splat(a1st, cs.y, cs.z);
+                    }
+                    commit = mh_commit_mode(o);
+                }
+                kind = cs.stage < 0 ? 4 : 2; // 4: between mutations -- resolved below
+            }
+            kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
+            v4_enqueue(L, qn, wantA, eAx, eAy, eAr, eAg, eAb);
+            v4_enqueue(L, qn, wantB, eBx, eBy, eBr, eBg, eBb);
+
+            // ---- commit: the chosen proposal's row group becomes the chain's x group
+            smp.adopt(commit);
+            roles = smp.roles();
+
+            // ---- start (parked chain lanes): the coins of the mutation that begins were drawn with the previous one
+            if (parked && kind == 1) {
+                const float *cn = &lds_x[L.coin_off + sub];
+                cs.large = cn[0] < C.p_large;
+                cs.coin_acc1 = cn[S]; cs.coin_acc2 = cn[2u * S]; cs.coin_mix = cn[3u * S];
+                cs.stage = 0;
+                cs.nd1 = cs.nd2 = 0u;
+            }
+
+            // ---- proposals of the chains that start a mutation, flattened: items (chain j, Philox block b) -> dimensions
+            // 4b..4b+3 of y; block nb1 = the four coins of the NEXT mutation
+            RowSampler smg = w2_sampler(Pm.key0, Pm.key1);
+            const uint32_t chain_base_g = Pm.chain_offset + blockIdx.x * 32u;
+            const uint32_t maj_mine = base + cs.it;
+            const unsigned info = roles | (cs.large ? 1u : 0u);
+            const uint32_t f1mask = (uint32_t) __ballot(kind == 1);
+            if (f1mask) {
+                if (kind == 1) lds_list[__builtin_amdgcn_mbcnt_lo(f1mask, 0u)] = (int) sub;
+                const uint32_t n = (uint32_t) __popc(f1mask), total = n * (nb1 + 1u);
+                const float rcp_n = 1.f / (float) n;
+                for (uint32_t fb = 0u; fb < total; fb += 64u) {
+                    const uint32_t i = fb + lane;
+                    const bool valid = i < total;
+                    const uint32_t ii = valid ? i : 0u;
+                    const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
+                    const uint32_t cj = (uint32_t) lds_list[j];
+                    const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
+                    const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
+                    smg.set_roles(inf, C.group, cj);
+#ifndef W2_TWO_PHILOX
+                    const bool coin = b >= nb1;
+                    if (valid) {
+                        const u4 r = philox4x32_10(Pm.key0, Pm.key1, coin ? 0u : b, coin ? mj + 1u : mj, chain_base_g + cj, coin ? TAG_COIN : TAG_S1);
+                        const Unit4 u{{u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)}};
+                        if (!coin) row_fill_first_drawn(smg, b, u, (inf & 1u) != 0u);
+                        else {
+                            float *dst = &lds_x[L.coin_off + cj];
+                            dst[0] = u.v[0]; dst[S] = u.v[1]; dst[2u * S] = u.v[2]; dst[3u * S] = u.v[3];
+                        }
+                    }
+#else
+                    if (valid) {
+                        if (b < nb1) smg.fill_first(b, mj, chain_base_g + cj, (inf & 1u) != 0u);
+                        else {
+                            const u4 coins = philox4x32_10(Pm.key0, Pm.key1, 0u, mj + 1u, chain_base_g + cj, TAG_COIN);
+                            float *dst = &lds_x[L.coin_off + cj];
+                            dst[0] = u32_to_unit(coins.x); dst[S] = u32_to_unit(coins.y); dst[2u * S] = u32_to_unit(coins.z); dst[3u * S] = u32_to_unit(coins.w);
+                        }
+                    }
+#endif
+                }
+            }
+            const uint32_t f2mask = (uint32_t) __ballot(kind == 2);
+            if (f2mask) { // second-stage proposals (rare: rejected bold steps)
+                if (kind == 2) lds_list[__builtin_amdgcn_mbcnt_lo(f2mask, 0u)] = (int) sub;
+                const uint32_t nb2 = Pm.timid_after_large ? D4 / 4u : (D4 / 2u + 3u) / 4u;
+                const uint32_t n = (uint32_t) __popc(f2mask), total = n * nb2;
+                const float rcp_n = 1.f / (float) n;
+                for (uint32_t fb = 0u; fb < total; fb += 64u) {
+                    const uint32_t i = fb + lane;
+                    const bool valid = i < total;
+                    const uint32_t ii = valid ? i : 0u;
+                    const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
+                    const uint32_t cj = (uint32_t) lds_list[j];
+                    const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
+                    const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
+                    smg.set_roles(inf, C.group, cj);
+                    if (valid) smg.fill_second(b, D4, mj, chain_base_g + cj, (inf & 1u) != 0u);
+                }
+            }
+
+            // ---- begin the evaluation (parked chain lanes): film position and camera ray from the first two components
+            if (parked) {
+                if (kind == 0) ps.phase = PH_IDLE;
+                else {
+                    DParams Vb{}; // what path_init and path_begin read of the block
+                    Vb.exclude_direct = C.exclude_direct; Vb.width = C.width; Vb.height = C.height;
+                    Vb.tan_half_fov = C.tan_half_fov; Vb.inv_aspect = C.inv_aspect; Vb.near_clip = C.near_clip; Vb.far_clip = C.far_clip;
+#pragma unroll
+                    for (int q = 0; q < 12; ++q) Vb.cam[q] = C.cam[q];
+                    smp_mode = smp.mode = cs.stage == 0 ? SM_STAGE1 : SM_STAGE2;
+                    path_init(Vb, ps);
+                    const float v0 = smp.next(0u), v1 = smp.next(1u);
+                    path_begin(Vb, ps, v0, v1);
+                }
+            }
+        }
+        // one ray per lane: chain lanes their camera / bounce ray, helpers the shadow ray they were handed
+        const bool tracing = helper ? helper_has_ray : ps.phase == PH_CLOSEST;
+        __builtin_amdgcn_s_setprio(0);
+        {
+            SECTION_PARAMS(Pt);
+            if (tracing) h = trace<0>(Pt, ps.o, ps.d, ps.tmin, ps.tmax, helper);
+        }
+        __builtin_amdgcn_s_setprio(3);
+        const unsigned occluded = from_upper_u((helper_has_ray && h.prim >= 0) ? 1u : 0u);
+        helper_has_ray = false;
+        ShadowRay sr;
+        sr.o = ps.o; sr.d = ps.d; sr.tmin = 0.f; sr.tmax = 0.f; sr.valid = false;
+        {
+            // no scalar load at the head of the step; its LDS reads still leave in three dependent trips (components, shading record, BSDF)
+            W2_SECTION(Cs);
+            if (!helper && ps.phase != PH_DONE && ps.phase != PH_IDLE) {
+                RowSampler sms = w2_sampler(0u, 0u);
+                sms.set_roles(roles, Cs.group, sub); sms.mode = smp_mode;
+                DParams Vs{}; // what path_step_diffuse reads of the block
+                Vs.eff_dim = Cs.eff_dim; Vs.rr_depth = Cs.rr_depth; Vs.max_depth = Cs.max_depth;
+                const LdsTables LT{Cs.shade_off, Cs.bsdf_off, 0u}; // (the emitter table is not read: HeldLightTables)
+                path_step_diffuse(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
+            }
+        }
+        // hand the shadow ray of this vertex to the helper lane
+        const float ox = from_lower(sr.o.x), oy = from_lower(sr.o.y), oz = from_lower(sr.o.z);
+        const float dx = from_lower(sr.d.x), dy = from_lower(sr.d.y), dz = from_lower(sr.d.z);
+        const float t0 = from_lower(sr.tmin), t1 = from_lower(sr.tmax);
+        const float vf = from_lower(sr.valid ? 1.f : 0.f);
+        if (helper) {
+            ps.o = mk3(ox, oy, oz); ps.d = mk3(dx, dy, dz); ps.tmin = t0; ps.tmax = t1;
+            helper_has_ray = vf != 0.f;
+        }
+    }
+    // the epilogue of k_mutate_v4, on its own copy of the block
+    SECTION_PARAMS(Pe);
+    const V4Layout<RULE_ORBITAL> Y = v4_layout<RULE_ORBITAL>(Pe, V4_QCAP);
+    if (qn + 32u > Y.L.qcap) v4_flush(Pe, Y.L, qn, lane);
+    v4_enqueue(Y.L, qn, live && cum > 0.f, cs.cur.px, cs.cur.py, cs.cur.r * cum, cs.cur.g * cum, cs.cur.b * cum);
+    v4_flush(Pe, Y.L, qn, lane);
+    if (live) {
+        RowSampler smp = Y.smp;
+        smp.set_roles(roles, Y.group, sub);
+        for (uint32_t k = 0; k < Y.D; ++k) Pe.x[(size_t) k * Pe.n_chains + c] = smp.x(k);
+        Pe.cur_lum[c] = cs.cur.lum; Pe.cur_px[c] = cs.cur.px; Pe.cur_py[c] = cs.cur.py;
+        Pe.cur_r[c] = cs.cur.r; Pe.cur_g[c] = cs.cur.g; Pe.cur_b[c] = cs.cur.b;
+        if (Pe.chain_done) Pe.chain_done[c] = base + cs.it;
+    }
+    if (Pe.chain_done && !reported && lane == 0) atomicSub(Pe.waves_left, 1u);
+    flush_counters(Pe, ct, lane);
+    const unsigned long long decided = wave_sum((live && !helper) ? cs.it : 0u);
+    if (lane == 0) atomicAdd(Pe.stats + 9, decided);
+}
+#undef W2_SECTION
+
+// ------------------------------------------------------------------------------------------
 // k_mutate_v5: the chain loop with MORE RAYS THAN LANES (all three types).
 //
 // In k_mutate_v4 a ray belongs to a lane: chain lane i traverses its camera / bounce ray, helper lane 32 + i the shadow ray
@@ -1520,7 +1866,10 @@ void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint
     // k_mutate_v4 <FEAT, LDS_TABLES, STAMPS, STACK16, OVF>: lane pairs, 32 chains per wave
     // (LAUNCH_RULE: the orbital twin of the build when the context's rule is the orbital one; LAUNCH_LIGHT: of either, the
     // one-light twin when the scene has one light)
-    case Build::V4_F0_STAMPS: LAUNCH_LIGHT(true, true); case Build::V4_F0: LAUNCH_LIGHT(true, false);
+    case Build::V4_F0_STAMPS: LAUNCH_LIGHT(true, true);
+    case Build::V4_F0: // (k_mutate_w2: the orbital one-light twin for launches without a third wave per SIMD -- plan.w2, launch_plan.h)
+        if (plan.w2 && orbital && one_light) { LAUNCH(k_mutate_w2); }
+        LAUNCH_LIGHT(true, false);
     case Build::V4_F3_STAMPS: LAUNCH(k_mutate_v4<3, true, true>); case Build::V4_F3: LAUNCH_RULE(3, true, false); case Build::V4_F7: LAUNCH_RULE(7, true, false);
     case Build::V4_F15_S32: LAUNCH(k_mutate_v4<15, true, false, false, true>); case Build::V4_F15_OVF: LAUNCH(k_mutate_v4<15, true, false, true, true>);
     case Build::V4_F15: LAUNCH(k_mutate_v4<15, true, false, true>);            case Build::V4_F7_GLOBAL: LAUNCH(k_mutate_v4<7, false, false>);

@@ -49,6 +49,7 @@ struct Knobs {
     size_t bdpt_lds_pad = 0;                 // DRMLT_BDPT_LDS_PAD: extra LDS bytes of every bdpt kernel (occupancy experiments)
     bool no_run_ahead = false;               // DRMLT_NO_RUN_AHEAD
     bool rule_generic = false;               // DRMLT_RULE_GENERIC: k_mutate_v4 runs its generic body whatever the rule (device_types.h: rule_is_orbital)
+    bool no_w2 = false;                      // DRMLT_NO_W2: the orbital one-light launches of V4_F0 stay on k_mutate_v4's twin (kernels.hip: k_mutate_w2)
     bool one_light_generic = false;          // DRMLT_ONE_LIGHT_GENERIC: k_mutate_v4 reads the light from the staged tables however many the scene has (device_types.h: scene_has_one_light)
     long long ahead_cap = -1;               // DRMLT_AHEAD_CAP: mutations a chain may run beyond the launch's target; -1 = min(8 slices, 8192)
     bool mmlt_no_sort = false, no_regroup = false, regroup_on_host = false, regroup_check = false; // DRMLT_MMLT_NO_SORT, _NO_REGROUP, _REGROUP_ON_HOST, _REGROUP_CHECK
@@ -61,7 +62,7 @@ inline Knobs read_knobs() {
         {"DRMLT_VERBOSE", &K.verbose}, {"DRMLT_BVH_STACK32", &K.bvh_stack32}, {"DRMLT_NO_QUAD_MERGE", &K.no_quad_merge}, {"DRMLT_NO_BOX_MERGE", &K.no_box_merge},
         {"DRMLT_NO_FLAT_LOOP", &K.no_flat_loop}, {"DRMLT_FEAT_ALL", &K.feat_all}, {"DRMLT_NO_SMALL_TABLES", &K.no_small_tables},
         {"DRMLT_MMLT_TABLES_GLOBAL", &K.mmlt_tables_global}, {"DRMLT_BDPT_TABLES_GLOBAL", &K.bdpt_tables_global}, {"DRMLT_NO_RUN_AHEAD", &K.no_run_ahead},
-        {"DRMLT_RULE_GENERIC", &K.rule_generic}, {"DRMLT_ONE_LIGHT_GENERIC", &K.one_light_generic},
+        {"DRMLT_RULE_GENERIC", &K.rule_generic}, {"DRMLT_ONE_LIGHT_GENERIC", &K.one_light_generic}, {"DRMLT_NO_W2", &K.no_w2},
         {"DRMLT_MMLT_NO_SORT", &K.mmlt_no_sort}, {"DRMLT_NO_REGROUP", &K.no_regroup}, {"DRMLT_REGROUP_ON_HOST", &K.regroup_on_host}, {"DRMLT_REGROUP_CHECK", &K.regroup_check}};
     for (const auto &f : flags) *f.on = getenv(f.name) != nullptr;
     int v = 0;
@@ -121,6 +122,7 @@ struct ChainPlan {
     int kernel_variant = 5, tables_in_lds = 0, small_tables_lds = 0;
     bool rows_mem = false;                   // k_mutate_v5's proposal rows in device memory (three waves per SIMD)
     int mh_batch = 0, trace_yield = 0, pool_refill = 0, trace_vote = 0;
+    bool w2 = false;                         // V4_F0 only: launch_mutate may run k_mutate_w2 in place of the orbital one-light twin (w2_launch below)
     bool run_ahead = false;                  // drmlt_run: chains run beyond a launch's target towards the call's total
     bool verbose = false;
     std::string note;                        // the DRMLT_VERBOSE line of the path kernels' launches
@@ -136,6 +138,13 @@ inline bool path_mh(const PlanInputs &in) { return in.technique == DRMLT_TECH_PA
 // 98 304 chains up it is the default -- Cornell: v5 2.15e9 at 131 072 chains, 1.11e9 at 65 536; v4 1.79e9 at 65 536, 1.55e9 at
 // 131 072. BASELINE's config 2 fixes 65 536 chains and therefore runs k_mutate_v4. With chains for more than two waves per SIMD
 // (from 163 840 per 256 CUs) its proposal rows move to device memory and it is built for three waves per SIMD: kernels.hip, ROWS_MEM.)
+// k_mutate_w2 (kernels.hip) is compiled for two waves per SIMD and spends the registers of a third on constants it would otherwise
+// re-read. It may replace a launch that can never have a third wave on a SIMD, for one of two reasons: the workgroup's LDS
+// exceeds a twelfth of a compute unit's 160 KB (four SIMDs x three waves), or the grid has no more than two waves per SIMD
+// of the device. The ONE place the condition is written down.
+constexpr size_t CU_LDS_BYTES = 160u * 1024u;
+inline bool w2_launch(size_t lds, uint32_t grid, int cus) { return lds * 12u > CU_LDS_BYTES || (uint64_t) grid <= (uint64_t) cus * 4u * 2u; }
+
 struct Family { int variant; bool tables_in_lds, rows_mem; };
 inline Family family(const PlanInputs &in, uint32_t n_chains, const Knobs &K) {
     Family f;
@@ -255,6 +264,7 @@ inline ChainPlan plan_chains(const PlanInputs &in, uint32_t n_chains, const Knob
         else
             p.build = (F & 8) == 0 ? Build::V4_F7_GLOBAL : !s16 ? (F == 8 ? Build::V4_F8_S32_GLOBAL : Build::V4_F15_S32_GLOBAL) : ovf ? Build::V4_F15_OVF_GLOBAL
                     : stamps ? Build::V4_F15_STAMPS_GLOBAL : F == 8 ? Build::V4_F8_GLOBAL : Build::V4_F15_GLOBAL;
+        p.w2 = p.build == Build::V4_F0 && !K.no_w2 && w2_launch(p.lds, p.grid, in.cus);
     } else { // k_mutate_v3, the cross-check: 32 chains per wave, rows of 32 floats; 0 = diffuse polygons, 3 = + rough conductor /
              // dielectric, 7 = + spheres, 15 = everything (BVH traversal); large scenes (tables in device memory): one general variant
         waves(32);
