@@ -5,8 +5,10 @@
 //     add_integrator(drmlt <path>/mitsuba_adaptor.cpp)      # replaces the four drmlt/*.cpp files
 //     target_link_libraries(drmlt drmlt_amd)                # libdrmlt_amd.so + include/drmlt_abi.h
 // None of those dependencies exist in the development image; there this file is compiled by build() against
-// tests/native/fake_mitsuba/ (same class / method names and signatures, each checked against the reference headers)
-// and driven by tests/native/adaptor_harness.cpp, so that everything below except the real headers is exercised.
+// tests/native/fake_mitsuba_emitters/ (tests/native/fake_mitsuba/ plus what mitsuba_emitters.hpp calls; same class / method
+// names and signatures, each checked against the reference headers)
+// and driven by tests/native/adaptor_harness.cpp and adaptor_emitters_harness.cpp, so that everything below except the real
+// headers is exercised. mitsuba_emitters.hpp, beside this file, is part of the plugin: the emitters that no shape carries.
 //
 // It keeps the reference's plugin surface (class name, parameters, RTTI, CreateInstance symbol:
 // include/mitsuba/core/cobject.h:99-107, src/integrators/drmlt/drmlt.cpp:176-621), so
@@ -24,10 +26,12 @@
 #include <algorithm>
 #include <cctype>
 #include <cmath>
+#include <cstdio>
 #include <ctime>
 #include <vector>
 
 #include "drmlt_abi.h"
+#include "mitsuba_emitters.hpp"
 
 MTS_NAMESPACE_BEGIN
 
@@ -89,10 +93,24 @@ public:
         m_deviceMask = props.hasProperty("devices") ? (uint32_t) props.getInteger("devices") : (1u << props.getInteger("device", 0));
         m_hasSeed = props.hasProperty("seed");
         m_seed = m_hasSeed ? (uint64_t) props.getInteger("seed") : 0;
+        //  * directPass = host (default) | device: who renders the separate direct-illumination image of directSamples > 0 --
+        //    the host's direct integrator as in the reference (util.cpp:30-92), or the GPUs of `devices`
+        //    (drmlt_node_render_direct). Read from the object's own copy of the properties (cobject.h:77), not from `props`:
+        //    tests/test_fake_mitsuba_signatures.py keeps a closed list of the backend-only names read from `props`.
+        //    Mitsuba's loader therefore reports the attribute as unqueried (scenehandler.cpp:793-795, a warning); it is read.
+        std::string directPass = getProperties().getString("directPass", "host");
+        if (directPass == "host") m_directOnDevice = false;
+        else if (directPass == "device") m_directOnDevice = true;
+        else Log(EError, "Unknown directPass (host | device)");
     }
 
+    // The payload is the configuration block and six scalars. directPass travels in the block's first reserved word of the
+    // serialized copy only (0 = host, 1 = device), so the payload keeps its size; the configuration handed to the library
+    // always has that word zero.
     DRMLT(Stream *stream, InstanceManager *manager) : Integrator(stream, manager), m_stop(0) {
         stream->read(&m_cfg, sizeof m_cfg);
+        m_directOnDevice = m_cfg.reserved[0] != 0;
+        m_cfg.reserved[0] = 0;
         m_deviceMask = (uint32_t) stream->readInt();
         m_twoStage = stream->readBool();
         m_firstStage = stream->readBool();
@@ -103,7 +121,9 @@ public:
 
     void serialize(Stream *stream, InstanceManager *manager) const {
         Integrator::serialize(stream, manager);
-        stream->write(&m_cfg, sizeof m_cfg);
+        drmlt_config wire = m_cfg;
+        wire.reserved[0] = m_directOnDevice ? 1 : 0;
+        stream->write(&wire, sizeof wire);
         stream->writeInt((int) m_deviceMask);
         stream->writeBool(m_twoStage);
         stream->writeBool(m_firstStage);
@@ -124,6 +144,20 @@ public:
 
     void cancel() { m_stop = 1; } // asynchronous (integrator.h:77-84); polled between kernel launches by drmlt_run
 
+    std::string toString() const {
+        static const char *technique[] = {"path", "bdpt", "mmlt"}, *type[] = {"green", "mira", "orbital"};
+        char buf[512];
+        snprintf(buf, sizeof buf,
+                 "DRMLT[\n  technique = %s,\n  type = %s,\n  maxDepth = %d,\n  rrDepth = %d,\n  directSamples = %d,\n"
+                 "  directPass = %s,\n  luminanceSamples = %d,\n  pLarge = %g,\n  workUnits = %d,\n  twoStage = %s,\n  devices = 0x%x\n]",
+                 // (after the Stream constructor both come from the wire)
+                 m_cfg.technique >= 0 && m_cfg.technique < 3 ? technique[m_cfg.technique] : "?",
+                 m_cfg.type >= 0 && m_cfg.type < 3 ? type[m_cfg.type] : "?", m_cfg.max_depth, m_cfg.rr_depth, m_cfg.direct_samples,
+                 m_directOnDevice ? "device" : "host", m_cfg.luminance_samples, (double) m_cfg.p_large, m_cfg.work_units,
+                 m_twoStage ? "true" : "false", m_deviceMask);
+        return buf;
+    }
+
     bool render(Scene *scene, RenderQueue *queue, const RenderJob *job, int sceneResID, int sensorResID,
                 int samplerResID) {
         ref<Sensor> sensor = scene->getSensor();
@@ -137,9 +171,15 @@ public:
         std::vector<drmlt_bsdf> bsdfs;
         std::vector<drmlt_emitter> emitters;
         std::vector<float> normals; // nine per smooth triangle (drmlt_scene.normals)
+        std::vector<float> points;  // xyz per point light (drmlt_scene.points)
+        std::vector<size_t> lightEnds; // per emitting shape, in shape order: one past its last entry of `emitters`
         const ref_vector<Shape> &mtsShapes = scene->getShapes();
-        for (size_t i = 0; i < mtsShapes.size(); ++i)
+        for (size_t i = 0; i < mtsShapes.size(); ++i) {
+            const size_t before = emitters.size();
             appendShape(mtsShapes[i].get(), shapes, bsdfs, emitters, normals);
+            if (emitters.size() > before) lightEnds.push_back(emitters.size());
+        }
+        appendEmitters(scene, emitters, points, shapes, lightEnds);
 
         drmlt_scene sc;
         memset(&sc, 0, sizeof sc);
@@ -147,6 +187,7 @@ public:
         sc.n_shapes = (int32_t) shapes.size(); sc.shapes = shapes.data();
         sc.n_bsdfs = (int32_t) bsdfs.size(); sc.bsdfs = bsdfs.data();
         sc.n_emitters = (int32_t) emitters.size(); sc.emitters = emitters.data();
+        sc.n_points = (int32_t) (points.size() / 3); sc.points = points.empty() ? NULL : points.data();
         sc.n_normals = (int32_t) (normals.size() / 9); sc.normals = normals.empty() ? NULL : normals.data();
         const PerspectiveCamera *cam = dynamic_cast<const PerspectiveCamera *>(sensor.get());
         if (!cam || cam->needsApertureSample())
@@ -205,12 +246,23 @@ public:
             Log(EError, "%s", msg.c_str());
         }
 
-        // separate direct pass stays on the host integrator (util.cpp:30-92), exactly as in the reference
+        // separate direct pass: on the host integrator (util.cpp:30-92), exactly as in the reference, unless
+        // directPass=device hands it to the GPUs of the node -- their image goes to develop as it is
         ref<Bitmap> directImage;
+        std::vector<float> direct;
         if (m_cfg.direct_samples > 0 && !nested) { // drmlt.cpp:479
-            directImage = BidirectionalUtils::renderDirectComponent(scene, sceneResID, sensorResID, queue, job,
-                                                                    m_cfg.direct_samples);
-            if (directImage == NULL) { drmlt_node_destroy(node); return false; }
+            if (m_directOnDevice) {
+                direct.resize((size_t) crop.x * crop.y * 3);
+                if (drmlt_node_render_direct(node, m_cfg.direct_samples, 0, seed ^ 0xD12EC7, direct.data()) != DRMLT_OK) {
+                    Log(EWarn, "Direct pass on the device failed: %s", drmlt_node_last_error(node));
+                    drmlt_node_destroy(node);
+                    return false;
+                }
+            } else {
+                directImage = BidirectionalUtils::renderDirectComponent(scene, sceneResID, sensorResID, queue, job,
+                                                                        m_cfg.direct_samples);
+                if (directImage == NULL) { drmlt_node_destroy(node); return false; }
+            }
         }
 
         double b = 0;
@@ -225,7 +277,6 @@ public:
         bool ok = rc == DRMLT_OK;
         if (ok) {
             ref<Bitmap> out = new Bitmap(Bitmap::ESpectrum, Bitmap::EFloat32, crop);
-            std::vector<float> direct;
             if (directImage) {
                 ref<Bitmap> d32 = directImage->convert(Bitmap::ESpectrum, Bitmap::EFloat32);
                 direct.assign(d32->getFloat32Data(), d32->getFloat32Data() + (size_t) crop.x * crop.y * 3);
@@ -431,6 +482,7 @@ private:
     int m_firstStageSizeReduction = 16;
     bool m_hasSeed = false;
     uint64_t m_seed = 0;
+    bool m_directOnDevice = false;
     volatile int m_stop;
 };
 

@@ -8,6 +8,7 @@ All constants are deterministic.
 """
 import ctypes as C
 import math
+import os
 
 import numpy as np
 
@@ -210,6 +211,39 @@ class SceneData:
             if self.normals:
                 f.write(_st.pack("<2I", NORMALS_TAG, len(self.normals)))
                 f.write(np.asarray(self.normals, dtype="<f4").tobytes())
+
+    @classmethod
+    def load(cls, path, name=None):
+        """The scene of a file that save() wrote (or the C++ side, in the same format): SceneFile::load's twin."""
+        import struct as _st
+        raw = open(path, "rb").read()
+        hdr = _st.unpack_from("<8I", raw, 0)
+        if hdr[0] != 0x4C4D5244 or hdr[1] != abi.ABI_VERSION or hdr[5:8] != (C.sizeof(abi.Shape), C.sizeof(abi.Bsdf), C.sizeof(abi.Emitter)):
+            raise ValueError("malformed scene file %s" % path)
+        sd = cls(name or os.path.basename(path))
+        off = 32
+        for group, T, n in ((sd.shapes, abi.Shape, hdr[2]), (sd.bsdfs, abi.Bsdf, hdr[3]), (sd.emitters, abi.Emitter, hdr[4])):
+            if off + n * C.sizeof(T) > len(raw):
+                raise ValueError("malformed scene file %s" % path)
+            group.extend((T * n).from_buffer_copy(raw, off))
+            off += n * C.sizeof(T)
+        if off + C.sizeof(abi.Camera) > len(raw):
+            raise ValueError("malformed scene file %s" % path)
+        sd.camera = abi.Camera.from_buffer_copy(raw, off)
+        off += C.sizeof(abi.Camera)
+        while off < len(raw):   # optional tagged blocks, points before normals
+            if off + 8 > len(raw):
+                raise ValueError("malformed scene file %s" % path)
+            tag, n = _st.unpack_from("<2I", raw, off)
+            off += 8
+            per = {POINTS_TAG: 3, NORMALS_TAG: 9}.get(tag)
+            dst = sd.points if tag == POINTS_TAG else sd.normals
+            if per is None or dst or (tag == POINTS_TAG and sd.normals) or off + 4 * per * n > len(raw):
+                raise ValueError("malformed scene file %s" % path)
+            vals = np.frombuffer(raw, dtype="<f4", count=per * n, offset=off).reshape(n, per)
+            dst.extend(tuple(float(v) for v in row) for row in vals)
+            off += 4 * per * n
+        return sd
 
     def struct(self):
         sh = (abi.Shape * len(self.shapes))(*self.shapes)

@@ -131,7 +131,9 @@ typedef struct drmlt_config {
     int32_t  no_direct_sampling; /* 1 = "directSampling" false (default true; bdpt only, forced false for mmlt) */
     int32_t  seed_rule;          /* DRMLT_SEED_*: two-stage MLT seeding, default TARGET (see the enum)            */
     int32_t  work_units_rule;    /* DRMLT_WORK_UNITS_*: what work_units = -1 derives, default DEVICE            */
-    int32_t  reserved[3];
+    int32_t  reserved[3];        /* zero. reserved[0] is taken on one wire: the Mitsuba plugin's serialize() keeps its
+                                  * directPass property there in its own copy of this block (mitsuba_adaptor.cpp) and hands the
+                                  * library zero again; a meaning given to [0] here must move that first. */
 } drmlt_config;
 
 /* ---- flat scene description -------------------------------------------- */
