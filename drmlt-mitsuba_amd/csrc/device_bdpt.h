@@ -93,6 +93,78 @@ struct BdptStore {
     }
 };
 
+// ------------------------------------------------------------------ PSS sampler triple of k_mutate_pssmlt_bdpt
+// Three PSSMLTSamplers (sensor, emitter, direct: pssmlt_proc.cpp:84-108) with MSampler's geometry: sensor rows [0, S) and emitter
+// rows [S, S + E) of the wave's LDS, the direct sampler's Dd components in memory. The per-component rule is PssmltSampler's
+// (device_sampler.h; pssmlt_sampler.h:113-143): a large step takes the uniform itself, a Kelemen step adds or subtracts
+// s2 (s1 / s2)^xi with TOROIDAL wrap, a Gaussian step is x + N(0, sigma) modulo 1 -- never wrap01, which reflects.
+// Draws: the TAG_S1 stream of (chain, mutation). Component k of a segment takes draw base + k (large, Kelemen) or draws
+// base + 2k, base + 2k + 1 (Gaussian), base = 0 (sensor), 2 Dmax (emitter), 4 Dmax (direct), Dmax = P.mmlt_dmax >= S, E: the
+// segments' ranges are disjoint whichever mutation runs. No oracle defines this
+// addressing. Every component exists from the seed on (k_init_chains_bdpt tops all three segments up), so there is no
+// lazily-created tail as in PssmltSampler: a component no path has read yet is an independent uniform either way.
+// A proposal is a pure function of (state, chain, mutation): the kernel commits it by asking for every component again.
+struct PssmltSampler3 {
+    uint32_t key0, key1, chain, major;
+    bool large, kelemen;
+    float sigma;
+    uint32_t lane;
+    float *x_dir;            // the direct sampler's state: column of this chain, row stride x_dir_n
+    uint32_t x_dir_n;
+    uint32_t S, E;
+    uint32_t base_e, base_d; // draw bases of the emitter / direct segments
+    int seg;
+    uint32_t x_off, draw_base;
+    uint32_t boot_k;         // (written by eval_bdpt for replayed streams; unused here)
+    u4 b1;
+    uint32_t b1_idx;
+
+    DEV void reset_caches() { b1_idx = 0xffffffffu; boot_k = 0u; }
+    DEV void select(int s) {
+        seg = s;
+        x_off = s == SEG_SENSOR ? 0u : (s == SEG_EMITTER ? S : S + E);
+        draw_base = s == SEG_SENSOR ? 0u : (s == SEG_EMITTER ? base_e : base_d);
+    }
+    DEV float u_s1(uint32_t idx) {
+        const uint32_t blk = idx >> 2;
+        if (blk != b1_idx) { b1 = philox4x32_10(key0, key1, blk, major, chain, TAG_S1); b1_idx = blk; }
+        return pick4(b1, idx & 3u);
+    }
+    DEV float x(uint32_t k) const {
+        if (seg == SEG_DIRECT) return x_dir[(size_t) k * x_dir_n];
+        return lds_x[(x_off + k) * 64u + lane];
+    }
+    DEV void put(uint32_t k, float v) const { // the state's component k of the active segment
+        if (seg == SEG_DIRECT) x_dir[(size_t) k * x_dir_n] = v;
+        else lds_x[(x_off + k) * 64u + lane] = v;
+    }
+    // primarySample(k) of the active segment
+    DEV float next(uint32_t k) {
+        if (large) return u_s1(draw_base + k);
+        float value = x(k);
+        if (kelemen) {
+            float xi = u_s1(draw_base + k);
+            const bool add = xi < 0.5f;
+            xi = add ? 2.f * xi : 2.f * (xi - 0.5f);
+            const float dv = KELEMEN_S2 * fast_exp2(xi * LOG2_S1_OVER_S2);
+            if (add) { value += dv; if (value > 1.f) value -= 1.f; }
+            else { value -= dv; if (value < 0.f) value += 1.f; }
+            return value;
+        }
+        const float v = value + gaussian_sample(u_s1(draw_base + 2u * k), u_s1(draw_base + 2u * k + 1u), sigma);
+        return v - floorf(v); // math::modulo(v, 1)
+    }
+};
+DEV void pssmlt3_setup(PssmltSampler3 &smp, const DParams &P, uint32_t lane, float *x_dir) {
+    smp.key0 = P.key0; smp.key1 = P.key1;
+    smp.large = false; smp.kelemen = P.kelemen_mutation != 0; smp.sigma = P.pss_sigma;
+    smp.lane = lane; smp.x_dir = x_dir; smp.x_dir_n = P.n_chains;
+    smp.S = (uint32_t) P.mmlt_S; smp.E = (uint32_t) P.mmlt_E;
+    smp.base_e = 2u * (uint32_t) P.mmlt_dmax; smp.base_d = 4u * (uint32_t) P.mmlt_dmax;
+    smp.reset_caches();
+    smp.select(SEG_SENSOR);
+}
+
 // Scene::pdfEmitterDirect under the AREA measure -- what PathVertex::evalPdfDirect(sample, EImportance, EArea) asks for
 // in Path::miWeight (vertex.cpp:1355-1382, scene.cpp:1057-1060, area.cpp:180-189, shape.cpp:118-127, sphere.cpp:356-385):
 // the density with which direct sampling from `ref` produces the emitter point (sp, sn)
@@ -132,8 +204,10 @@ DEV int bdpt_row_cells(const DParams &P, int s, int nS, int &maxT) {
     return max(0, maxT - minT + 1);
 }
 
-template <int FEAT = 15, class TablesT>
-DEV void eval_bdpt(const DParams &P, const TablesT &T, MSampler &smp, bool active, uint32_t chain, uint32_t mis_row, float *list, BdptResult &R) {
+// SamplerT: MSampler (the delayed-rejection chains, bootstrap, replay, evaluation points) or PssmltSampler3 (algo=pssmlt) -- what
+// the evaluation asks of it: lane, reset_caches(), select(segment), next(k), boot_k.
+template <int FEAT = 15, class TablesT, class SamplerT>
+DEV void eval_bdpt(const DParams &P, const TablesT &T, SamplerT &smp, bool active, uint32_t chain, uint32_t mis_row, float *list, BdptResult &R) {
     const uint32_t lane = smp.lane, n = P.n_chains_alloc;
     const int ME = P.max_depth, MS = P.max_depth + 1;
     const uint32_t NVS = (uint32_t) (ME + MS);

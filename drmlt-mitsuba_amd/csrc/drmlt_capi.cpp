@@ -36,6 +36,8 @@ void launch_bootstrap_bdpt(const DParams &P, uint32_t n, float *lum_out, size_t 
 void launch_init_chains_bdpt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, size_t lds, hipStream_t st);
 void launch_mutate_bdpt(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
 void launch_eval_lists_bdpt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out, uint32_t stride, size_t lds, hipStream_t st);
+// algo=pssmlt over technique=bdpt (kernels_pssmlt_bdpt.hip); bootstrap, seed replay and evaluation are technique=bdpt's
+void launch_mutate_pssmlt_bdpt(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
 void launch_render_pt(const DParams &P, uint64_t n_samples, uint32_t stream, float scale, hipStream_t st);
 // the direct-illumination pass (kernels_direct.hip)
 uint32_t direct_grid(const DirectJob &J, int width);
@@ -113,8 +115,8 @@ drmlt_ctx *drmlt_create(const drmlt_config *cfg, const drmlt_scene *scene, int d
     scene = &scene_in;
     // ---- parameter checks of the DRMLT ctor / PathSampler ctor (drmlt.cpp:193-349, pathsampler.cpp:57-71)
     if (cfg->algo != DRMLT_ALGO_DRMLT && cfg->algo != DRMLT_ALGO_PSSMLT) return bail(nullptr, "Unknown algorithm");
-    if (cfg->algo == DRMLT_ALGO_PSSMLT && cfg->technique != DRMLT_TECH_PATH)
-        return bail(nullptr, "algo=pssmlt runs over technique=path on the device (BASELINE config 1)");
+    if (cfg->algo == DRMLT_ALGO_PSSMLT && cfg->technique == DRMLT_TECH_MMLT)
+        return bail(nullptr, "algo=pssmlt runs over technique=path (BASELINE config 1) and technique=bdpt on the device, not over technique=mmlt");
     if (cfg->technique != DRMLT_TECH_PATH && cfg->technique != DRMLT_TECH_BDPT && cfg->technique != DRMLT_TECH_MMLT)
         return bail(nullptr, "Unknown technique type");
     if (cfg->type < DRMLT_TYPE_GREEN || cfg->type > DRMLT_TYPE_ORBITAL) return bail(nullptr, "Unknown implementation type");
@@ -369,7 +371,8 @@ static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint3
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // `order` is a local
         ctx->P.exec_order = P.exec_order = ctx->d_order.as<uint32_t>();
     }
-    if (bdpt && !ctx->knobs.no_regroup) { // execution order of k_mutate_bdpt: identity until the first launch has told the chains' work apart (regroup_chains)
+    // (k_mutate_pssmlt_bdpt keeps exec_order NULL: one evaluation per mutation, nothing tells the chains' work apart)
+    if (bdpt && ctx->cfg.algo != DRMLT_ALGO_PSSMLT && !ctx->knobs.no_regroup) { // execution order of k_mutate_bdpt: identity until the first launch has told the chains' work apart (regroup_chains)
         const uint32_t n = ctx->n_chains, padded = (n + 63u) / 64u * 64u;
         std::vector<uint32_t> order(padded, n);
         for (uint32_t j = 0; j < n; ++j) order[j] = j;
@@ -595,6 +598,7 @@ int drmlt_run(drmlt_ctx *ctx, uint64_t total_mutations, volatile int *stop, drml
             DParams Q = ctx->P;
             if (regroup) Q.chain_done = ctx->d_done.as<uint32_t>(); // per-chain evaluation counts of this launch
             if (ctx->cfg.technique == DRMLT_TECH_MMLT) launch_mutate_mmlt(plan, Q, n, ctx->mutation_base, ctx->stream);
+            else if (ctx->cfg.algo == DRMLT_ALGO_PSSMLT) launch_mutate_pssmlt_bdpt(plan, Q, n, ctx->mutation_base, ctx->stream);
             else launch_mutate_bdpt(plan, Q, n, ctx->mutation_base, ctx->stream);
         }
         else if (ahead) {

@@ -12,7 +12,7 @@
 #include <cstdlib>
 #include <string>
 
-// ---- LDS layout constants and formulas (kernels.hip, kernels_mmlt.hip, kernels_bdpt.hip)
+// ---- LDS layout constants and formulas (kernels.hip, kernels_mmlt.hip, kernels_bdpt.hip, kernels_pssmlt_bdpt.hip)
 constexpr uint32_t V4_STRIDE = 33u;   // row stride of the sampler rows: (row + chain) mod 32 banks serve per-chain AND per-dimension access patterns
 constexpr uint32_t V4_QCAP = 160u;    // splat queue entries: flushed when a bookkeeping branch (at most 2 x 32 new entries) might not fit
 constexpr uint32_t V4_QCAP_BVH = 100u; // BVH scenes: their kernel also keeps the traversal stack in LDS (6 KB); flushes are a negligible part of it
@@ -112,6 +112,7 @@ enum class Build {
     V3_F0, V3_F3, V3_F7, V3_F15, V3_F15_GLOBAL,
     MMLT_F7_TABLES, MMLT_F15, MMLT_F7,
     BDPT_F15, BDPT_F7_OCC2_TABLES, BDPT_F7_OCC2, BDPT_F7,
+    PSSMLT_BDPT_F15, PSSMLT_BDPT_F7_OCC2_TABLES, PSSMLT_BDPT_F7_OCC2, PSSMLT_BDPT_F7, // algo=pssmlt over technique=bdpt (kernels_pssmlt_bdpt.hip)
 };
 
 struct ChainPlan {
@@ -162,7 +163,7 @@ inline Family family(const PlanInputs &in, uint32_t n_chains, const Knobs &K) {
 // work_units_rule = DRMLT_WORK_UNITS_REFERENCE restores that formula. The device's counts, never chains shorter than 64 mutations:
 // - path: 196 608 when the pool kernel runs three 64-chain waves per SIMD at that count (traversed scenes, whose node fetches the
 //   extra wave covers, + 4 % (2000 triangles) ... + 17 % (50 000, 1 000 000); flat scenes + 20 %: DESIGN section 6), else 131 072
-//   (two waves of the pool kernel); 65 536 for a kernel chosen by DRMLT_KERNEL and for pssmlt;
+//   (two waves of the pool kernel); 65 536 for a kernel chosen by DRMLT_KERNEL and for pssmlt (over path and over bdpt);
 // - bdpt: 131 072 (one chain per lane; its workspace is 2 KB per chain and loses with more than fill the device);
 // - mmlt: MANY rounds of waves, run in depth order -- 262 144 chains 2.56e9 mutations/s on BASELINE's config 5, 524 288 2.79e9,
 //   1 048 576 2.91e9. The price is paid before the first mutation: 50 x maxDepth bootstrap samples per chain (drmlt.cpp:456-473),
@@ -177,7 +178,8 @@ inline uint32_t derive_chains(const PlanInputs &in, const Knobs &K) {
         return (uint32_t) std::max<uint64_t>(1, (in.budget + per_unit - 1) / per_unit);
     }
     uint64_t fill = 65536;
-    if (mmlt) fill = in.budget >= (1ull << 35) ? 1048576 : 262144;
+    if (in.algo == DRMLT_ALGO_PSSMLT) fill = 65536;
+    else if (mmlt) fill = in.budget >= (1ull << 35) ? 1048576 : 262144;
     else if (bdpt) fill = 131072;
     else if (plan_detail::path_mh(in) && !K.kernel) fill = plan_detail::family(in, 196608, K).rows_mem ? 196608 : 131072;
     return (uint32_t) std::min<uint64_t>(fill, std::max<uint64_t>(64, in.budget / 64 / 64 * 64));
@@ -232,6 +234,9 @@ inline ChainPlan plan_chains(const PlanInputs &in, uint32_t n_chains, const Knob
         if (bvh) p.build = Build::BDPT_F15;
         else if (two && !K.bdpt_tables_global && p.lds + tb <= 20480) p.build = Build::BDPT_F7_OCC2_TABLES, p.lds += tb;
         else p.build = two ? Build::BDPT_F7_OCC2 : Build::BDPT_F7;
+        if (pssmlt) // k_mutate_pssmlt_bdpt: the same rows, the same tables, the same occupancy rule -- its own loop
+            p.build = p.build == Build::BDPT_F15 ? Build::PSSMLT_BDPT_F15 : p.build == Build::BDPT_F7_OCC2_TABLES ? Build::PSSMLT_BDPT_F7_OCC2_TABLES
+                    : p.build == Build::BDPT_F7_OCC2 ? Build::PSSMLT_BDPT_F7_OCC2 : Build::PSSMLT_BDPT_F7;
     } else if (pssmlt) {
         waves(64);
         p.lds = D * 64 * sizeof(float);

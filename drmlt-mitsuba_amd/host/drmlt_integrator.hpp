@@ -114,7 +114,11 @@ public:
     explicit DRMLTIntegrator(const Properties &props) {
         memset(&m_cfg, 0, sizeof m_cfg);
         m_cfg.struct_size = sizeof m_cfg;
-        m_cfg.algo = DRMLT_ALGO_DRMLT;
+        // which of the reference's two integrators: drmlt (drmlt.cpp) or pssmlt (pssmlt.cpp; over path and bdpt on the device)
+        std::string integrator = props.getString("integrator", "drmlt");
+        if (integrator == "drmlt") m_cfg.algo = DRMLT_ALGO_DRMLT;
+        else if (integrator == "pssmlt") m_cfg.algo = DRMLT_ALGO_PSSMLT;
+        else throw std::runtime_error("Unknown integrator (drmlt | pssmlt)");
         std::string technique = props.getString("technique");
         if (technique == "path") m_cfg.technique = DRMLT_TECH_PATH;
         else if (technique == "bdpt") m_cfg.technique = DRMLT_TECH_BDPT;
@@ -137,7 +141,7 @@ public:
         // :228-231 (forced off for mmlt). bdpt: the device builds the directSampling=false variant only (see drmlt_create)
         m_cfg.no_direct_sampling = (props.getBoolean("directSampling", true) && m_cfg.technique != DRMLT_TECH_MMLT) ? 0 : 1;
         m_cfg.average_luminance = (float) props.getFloat("averageLuminance", -1.0);
-        std::string type = props.getString("type");
+        std::string type = m_cfg.algo == DRMLT_ALGO_PSSMLT ? props.getString("type", "orbital") : props.getString("type"); // (pssmlt has no delayed rejection: unused)
         if (type == "green") m_cfg.type = DRMLT_TYPE_GREEN;
         else if (type == "mira") m_cfg.type = DRMLT_TYPE_MIRA;
         else if (type == "mirasym" || type == "orbital") m_cfg.type = DRMLT_TYPE_ORBITAL;
@@ -151,7 +155,7 @@ public:
         m_cfg.sigma = (float) props.getFloat("sigma", 1.0 / 64.0);
         m_cfg.scale_second = (float) props.getFloat("scaleSecond", 0.1);
         if (m_cfg.scale_second > 1.0f) throw std::runtime_error("scaleSecond is bigger than the first stage");
-        m_cfg.kelemen_style_mutation = 1;
+        m_cfg.kelemen_style_mutation = props.getBoolean("kelemenStyleMutation", true) ? 1 : 0; // pssmlt.cpp: Kelemen (true) or Gaussian mutation
         m_cfg.sample_count = props.getInteger("sampleCount", 4); // the independent sampler's sampleCount (default 4)
         m_device = props.getInteger("device", 0);
         m_seed = (uint64_t) props.getInteger("seed", 0x5EED);

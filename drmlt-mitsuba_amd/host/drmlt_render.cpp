@@ -1,7 +1,8 @@
 // drmlt_render: `mitsuba scene.xml -D key=value -o out` in miniature for the MI355X backend.
 //   drmlt_render scene.bin -D technique=path -D type=orbital -D maxDepth=8 -D sampleCount=64 -o out.pfm
 //   drmlt_render --check -D ...      parse the parameters only (no GPU needed), print the configuration
-// -D pairs are the plugin parameters of the reference (README.md:95-104, drmlt.cpp:193-349).
+// -D pairs are the plugin parameters of the reference (README.md:95-104, drmlt.cpp:193-349); integrator=pssmlt|drmlt (default drmlt)
+// picks the chain loop, and kelemenStyleMutation / kelemenStyleWeights are pssmlt's.
 #include "drmlt_integrator.hpp"
 
 #include <cstdlib>
@@ -29,9 +30,10 @@ int main(int argc, char **argv) {
         const drmlt_config &c = integrator.config();
         if (check) {
             printf("technique=%d type=%d maxDepth=%d rrDepth=%d directSamples=%d luminanceSamples=%d pLarge=%g workUnits=%d "
-                   "sigma=%g scaleSecond=%g acceptanceMap=%d timidAfterLarge=%d useMixture=%d sampleCount=%d\n",
+                   "sigma=%g scaleSecond=%g acceptanceMap=%d timidAfterLarge=%d useMixture=%d sampleCount=%d integrator=%s kelemenStyleMutation=%d kelemenStyleWeights=%d\n",
                    c.technique, c.type, c.max_depth, c.rr_depth, c.direct_samples, c.luminance_samples, c.p_large, c.work_units,
-                   c.sigma, c.scale_second, c.acceptance_map, c.timid_after_large, c.use_mixture, c.sample_count);
+                   c.sigma, c.scale_second, c.acceptance_map, c.timid_after_large, c.use_mixture, c.sample_count,
+                   c.algo == DRMLT_ALGO_PSSMLT ? "pssmlt" : "drmlt", c.kelemen_style_mutation, c.kelemen_style_weights);
             return 0;
         }
         if (scene.empty()) throw std::runtime_error("no scene file given");

@@ -17,7 +17,9 @@
  *                     src/integrators/drmlt/drmlt.cpp:498-546,
  *                     src/integrators/drmlt/drmlt_proc.cpp:467-514
  *   drmlt_run         DRMLTRenderer::process / processMixture (the chain loop)
- *                     src/integrators/drmlt/drmlt_proc.cpp:161-380,386-771
+ *                     src/integrators/drmlt/drmlt_proc.cpp:161-380,386-771;
+ *                     algo=pssmlt: PSSMLTRenderer::process
+ *                     src/integrators/pssmlt/pssmlt_proc.cpp:110-285
  *   drmlt_develop     DRMLTProcess::develop
  *                     src/integrators/drmlt/drmlt_proc.cpp:813-854
  *   drmlt_stats       the StatsCounter block
@@ -54,7 +56,7 @@ enum { DRMLT_TECH_PATH = 0, DRMLT_TECH_BDPT = 1, DRMLT_TECH_MMLT = 2 };
 /* DRMLTConfiguration::EType, src/integrators/drmlt/drmlt.h:70-74 */
 enum { DRMLT_TYPE_GREEN = 0, DRMLT_TYPE_MIRA = 1, DRMLT_TYPE_ORBITAL = 2 };
 
-/* which chain loop: drmlt_proc.cpp (0) or pssmlt_proc.cpp (1, oracle only) */
+/* which chain loop: drmlt_proc.cpp (0) or pssmlt_proc.cpp (1: over technique=path and technique=bdpt on the device; mmlt is refused) */
 enum { DRMLT_ALGO_DRMLT = 0, DRMLT_ALGO_PSSMLT = 1 };
 
 enum { DRMLT_SHAPE_TRIANGLE = 0, DRMLT_SHAPE_RECTANGLE = 1, DRMLT_SHAPE_SPHERE = 2 };
