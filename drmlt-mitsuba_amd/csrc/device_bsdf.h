@@ -6,8 +6,10 @@
 #pragma once
 #include "device_math.h"
 
-// exp / log on the hardware's base-2 units (~2e-6 relative over the ranges used here, against 1e-7 for libm's):
-// the microfacet sampler's Newton loop evaluates them up to ten times per sample
+// exp / log on the hardware's base-2 units, against 1e-7 for libm's: the microfacet sampler's Newton loop evaluates them up to
+// ten times per sample. Measured on the device (tests/test_gpu_bsdf.py pins the figures): rc_exp is off by |x| * 2^-24 in the
+// exponent, the rounding of x * log2(e) -- 4.7e-7 relative over [-10, 0], 3.8e-6 at x = -87 --; rc_log by 1.5e-7 relative
+// over [1e-7, 1] (1.0e-7 absolute where |log x| < 1).
 DEV float rc_exp(float x) { return fast_exp2(x * 1.4426950408889634f); }
 DEV float rc_log(float x) { return fast_log2(x) * 0.6931471805599453f; }
 DEV float mts_erfinv(float x) {

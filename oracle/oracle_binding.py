@@ -341,6 +341,60 @@ def roughconductor(ggx, alpha, eta, k, wi, wo=None, sxy=None):
     return dict(eval=ev, pdf=pdf, wo=swo, weight=sw, spdf=spdf)
 
 
+BSDF_PROBE_COLS = 25
+
+
+def bsdf_probe(precision, ggx, alpha, eta, k, wi, wo=None, m=None, sxy=None, specular_reflectance=(1, 1, 1)):
+    """roughconductor() with one wi per sample, in float (precision 32) or double (64) arithmetic: eval / pdf of (wi, wo) and of
+    (wo, wi), the sample for (sx, sy) with the sampled normal, eval and pdf at the sampled direction, and D(m), G1(wi, m),
+    pdfVisible(wi, m). Inputs are rounded to the precision first; the results come back as float64."""
+    f = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    p = lambda a: None if a is None else a.ctypes.data
+    eta, k, refl, wi, wo, m, sxy = f(eta), f(k), f(specular_reflectance), f(wi), f(wo), f(m), f(sxy)
+    n = len(wi)
+    assert wi.shape == (n, 3) and all(a is None or len(a) == n for a in (wo, m, sxy))
+    out = np.zeros((n, BSDF_PROBE_COLS))
+    L = lib()
+    L.oracle_bsdf_probe.argtypes = [C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 5
+    if L.oracle_bsdf_probe(precision, int(ggx), alpha, p(eta), p(k), p(refl), n, p(wi), p(wo), p(m), p(sxy), p(out)) != 0:
+        raise OracleError("bsdf_probe: precision must be 32 or 64")
+    return dict(eval=out[:, 0:3], pdf=out[:, 3], eval_rev=out[:, 4:7], pdf_rev=out[:, 7], wo=out[:, 8:11], weight=out[:, 11:14],
+                spdf=out[:, 14], m=out[:, 15:18], D=out[:, 18], G1=out[:, 19], pdf_visible=out[:, 20], pdf_at_wo=out[:, 21],
+                eval_at_wo=out[:, 22:25])
+
+
+def _elementwise(name, precision, args, cols, *ints):
+    args = [np.ascontiguousarray(a, dtype=np.float64) for a in args]
+    n = len(args[0])
+    out = np.zeros((n, cols)) if cols > 1 else np.zeros(n)
+    fn = getattr(lib(), name)
+    fn.argtypes = [C.c_int] * (1 + len(ints)) + [C.c_uint32] + [C.c_void_p] * (len(args) + 1)
+    if fn(precision, *ints, n, *[a.ctypes.data for a in args], out.ctypes.data) != 0:
+        raise OracleError("%s: precision must be 32 or 64" % name)
+    return out
+
+
+def fresnel_conductor(precision, cos_i, eta, k):
+    """fresnelConductorExact, element by element."""
+    return _elementwise("oracle_fresnel_probe", precision, np.broadcast_arrays(cos_i, eta, k), 1, 0)
+
+
+def fresnel_dielectric(precision, cos_i, eta):
+    """fresnelDielectricExt, element by element: (F, cosThetaT)."""
+    c, e = np.broadcast_arrays(cos_i, eta)
+    out = _elementwise("oracle_fresnel_probe", precision, (c, e, e), 2, 1)
+    return out[:, 0], out[:, 1]
+
+
+def cosine_hemisphere(precision, sxy):
+    return _elementwise("oracle_warp_probe", precision, (sxy,), 3)
+
+
+def mts_erf(precision, x, inverse=False):
+    """Mitsuba's erf / erfinv approximations (math.cpp:25-72)."""
+    return _elementwise("oracle_erf_probe", precision, (x,), 1, int(inverse))
+
+
 def luminance_map(rgb_small, width, height):
     src = np.ascontiguousarray(rgb_small, dtype=np.float32)
     out = np.empty((height, width), dtype=np.float32)

@@ -675,6 +675,83 @@ void oracle_roughconductor(int ggx, double alpha, const double *eta, const doubl
     }
 }
 
+} // extern "C"
+
+// The same with one wi per sample, in float or double arithmetic, with the reflectance and the distribution's own terms.
+// Each of wo_in, m_in, sxy may be null; a row of `out` (BSDF_PROBE_COLS doubles) holds
+//   0-2 eval(wi, wo_in), 3 pdf(wi, wo_in), 4-6 eval(wo_in, wi), 7 pdf(wo_in, wi),
+//   8-10 sampled wo, 11-13 weight, 14 the sample's pdf (0 where the weight is 0), 15-17 sampleVisible(wi),
+//   18 D(m_in), 19 G1(wi, m_in), 20 pdfVisible(wi, m_in), 21 pdf(wi, sampled wo), 22-24 eval(wi, sampled wo)
+enum { BSDF_PROBE_COLS = 25 };
+template <typename F> static void bsdfProbe(int ggx, double alpha, const double *eta, const double *k, const double *refl, uint32_t n,
+                                            const double *wi, const double *wo_in, const double *m_in, const double *sxy, double *out) {
+    auto v3 = [](const double *p) { return V3<F>((F) p[0], (F) p[1], (F) p[2]); };
+    auto put3 = [](double *o, const V3<F> &v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; };
+    const RoughConductor<F> rc{Microfacet<F>(ggx != 0, (F) alpha), v3(eta), v3(k), v3(refl)};
+    for (uint32_t i = 0; i < n; ++i) {
+        const V3<F> w = v3(wi + 3 * i);
+        double *o = out + (size_t) BSDF_PROBE_COLS * i;
+        if (wo_in) {
+            const V3<F> wo = v3(wo_in + 3 * i);
+            put3(o, rc.eval(w, wo)); o[3] = rc.pdf(w, wo);
+            put3(o + 4, rc.eval(wo, w)); o[7] = rc.pdf(wo, w);
+        }
+        if (sxy) {
+            V3<F> wo(0);
+            F pdf = 0;
+            const V3<F> wt = rc.sample(w, (F) sxy[2 * i], (F) sxy[2 * i + 1], wo, pdf);
+            put3(o + 8, wo); put3(o + 11, wt); o[14] = wt.isZero() ? 0.0 : (double) pdf;
+            put3(o + 15, rc.distr.sampleVisible(w, (F) sxy[2 * i], (F) sxy[2 * i + 1]));
+            if (!wt.isZero()) { o[21] = rc.pdf(w, wo); put3(o + 22, rc.eval(w, wo)); }
+        }
+        if (m_in) {
+            const V3<F> m = v3(m_in + 3 * i);
+            o[18] = rc.distr.eval(m); o[19] = rc.distr.smithG1(w, m); o[20] = rc.distr.pdfVisible(w, m);
+        }
+    }
+}
+
+// fresnelConductorExact (kind 0: out = F) and fresnelDielectricExt (kind 1: out = F, cosThetaT; k is not read), element by element
+template <typename F> static void fresnelProbe(int kind, uint32_t n, const double *cosI, const double *eta, const double *k, double *out) {
+    for (uint32_t i = 0; i < n; ++i) {
+        if (kind == 0) out[i] = fresnelConductorExact((F) cosI[i], (F) eta[i], (F) k[i]);
+        else { F ct = 0; out[2 * i] = fresnelDielectricExt((F) cosI[i], ct, (F) eta[i]); out[2 * i + 1] = ct; }
+    }
+}
+
+extern "C" {
+
+int oracle_bsdf_probe(int precision, int ggx, double alpha, const double *eta, const double *k, const double *specular_reflectance, uint32_t n,
+                      const double *wi, const double *wo_in, const double *m_in, const double *sxy, double *out) {
+    if (precision == 32) bsdfProbe<float>(ggx, alpha, eta, k, specular_reflectance, n, wi, wo_in, m_in, sxy, out);
+    else if (precision == 64) bsdfProbe<double>(ggx, alpha, eta, k, specular_reflectance, n, wi, wo_in, m_in, sxy, out);
+    else return -1;
+    return 0;
+}
+
+int oracle_fresnel_probe(int precision, int kind, uint32_t n, const double *cosI, const double *eta, const double *k, double *out) {
+    if (precision == 32) fresnelProbe<float>(kind, n, cosI, eta, k, out);
+    else if (precision == 64) fresnelProbe<double>(kind, n, cosI, eta, k, out);
+    else return -1;
+    return 0;
+}
+
+// squareToCosineHemisphere and the scalar approximations (0 erf, 1 erfinv), element by element
+int oracle_warp_probe(int precision, uint32_t n, const double *sxy, double *out) {
+    for (uint32_t i = 0; i < n; ++i) {
+        if (precision == 32) { V3<float> d = squareToCosineHemisphere((float) sxy[2 * i], (float) sxy[2 * i + 1]); out[3 * i] = d.x; out[3 * i + 1] = d.y; out[3 * i + 2] = d.z; }
+        else { V3<double> d = squareToCosineHemisphere(sxy[2 * i], sxy[2 * i + 1]); out[3 * i] = d.x; out[3 * i + 1] = d.y; out[3 * i + 2] = d.z; }
+    }
+    return 0;
+}
+int oracle_erf_probe(int precision, int inverse, uint32_t n, const double *x, double *out) {
+    for (uint32_t i = 0; i < n; ++i) {
+        if (precision == 32) out[i] = inverse ? mts_erfinv((float) x[i]) : mts_erf((float) x[i]);
+        else out[i] = inverse ? mts_erfinv(x[i]) : mts_erf(x[i]);
+    }
+    return 0;
+}
+
 int oracle_bdpt_render(void *p, uint64_t n, uint64_t seed, int nthreads, float *out) { GUARD(static_cast<CtxBase *>(p)->bdptRender(n, seed, nthreads, out)) }
 int oracle_bdpt_eval(void *p, const float *uSensor, const float *uEmitter, const float *uDirect, uint32_t n, uint32_t dim, float *out, uint32_t stride) { GUARD(static_cast<CtxBase *>(p)->bdptEval(uSensor, uEmitter, uDirect, n, dim, out, stride)) }
 int oracle_set_importance_map(void *p, const float *map) { GUARD(static_cast<CtxBase *>(p)->setImportance(map)) }
