@@ -29,7 +29,7 @@ ABI_SYMBOLS = (
     "drmlt_node_create", "drmlt_node_seed", "drmlt_node_run", "drmlt_node_develop", "drmlt_node_stats_get",
     "drmlt_node_set_importance_map", "drmlt_node_device_count", "drmlt_node_context", "drmlt_node_last_error",
     "drmlt_node_destroy", "drmlt_bootstrap_luminances", "drmlt_seed_indices", "drmlt_comm_info", "drmlt_film_tile",
-    "drmlt_render_direct", "drmlt_direct_split", "drmlt_node_render_direct",
+    "drmlt_render_direct", "drmlt_direct_split", "drmlt_node_render_direct", "drmlt_render_bdpt",
 )
 
 
@@ -79,6 +79,7 @@ def load_library():
     L.drmlt_set_stream.argtypes = [C.c_void_p, C.c_void_p]
     L.drmlt_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
     L.drmlt_render_pt.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+    L.drmlt_render_bdpt.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
     L.drmlt_chain_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.drmlt_last_error.restype = C.c_char_p
     L.drmlt_last_error.argtypes = [C.c_void_p]
@@ -297,6 +298,14 @@ class Context:
         self._chk(self.L.drmlt_render_pt(self.h, spp, seed, out.ctypes.data))
         return out
 
+    def render_bdpt(self, spp, seed=1):
+        """technique=bdpt: spp * W * H independent samples of sampleSplats(EBidirectional), every splat of every list filtered into
+        an (H, W, 3) image of develop's expectation. Sample i is bootstrap sample i of stream 0 under `seed`
+        (bootstrap_luminances); the context's film and chains are left alone."""
+        out = np.empty((self.height, self.width, 3), dtype=np.float32)
+        self._chk(self.L.drmlt_render_bdpt(self.h, spp, seed, out.ctypes.data))
+        return out
+
     def render_direct(self, direct_samples=None, hide_emitters=False, seed=1, rows=None):
         """The direct-illumination image develop(direct=...) adds (renderDirectComponent): rows [rows[0], rows[1]) of it, the
         whole frame by default. direct_samples defaults to the configuration's."""
@@ -368,6 +377,18 @@ def direct_split(direct_samples):
     if rc != 0:
         raise DrmltError(rc, "directSamples must be positive (got %d): no direct image is rendered" % direct_samples)
     return ps.value, ss.value
+
+
+def visible_emitter_mask(scene_data, seeds=64, device=0):
+    """(H, W) bool: the pixels in which some camera ray meets an emitter, and their eight neighbours -- render_direct with and
+    without the emitters the camera sees, `seeds` renders of 8 pixel positions each. technique=path adds no emitted light on camera
+    rays and technique=mmlt drops it, the bidirectional integrand (render_bdpt) has it: under the box filter that light lies in
+    these pixels alone, so a comparison across the two leaves them out."""
+    lumw = np.array([0.212671, 0.715160, 0.072169])
+    with Context(abi.make_config(technique="path", max_depth=2, direct_samples=-1, work_units=64, luminance_samples=1000), scene_data, device) as ctx:
+        seen = sum((ctx.render_direct(8, seed=s).astype(np.float64) - ctx.render_direct(8, hide_emitters=True, seed=s)) @ lumw for s in range(seeds))
+    m = np.pad(seen > 0, 1)
+    return np.any([m[1 + dy:m.shape[0] - 1 + dy, 1 + dx:m.shape[1] - 1 + dx] for dy in (-1, 0, 1) for dx in (-1, 0, 1)], axis=0)
 
 
 def comm_unique_id():
@@ -449,7 +470,7 @@ class Node:
         return self.context(rank).film()
 
     def context(self, rank):
-        """Rank `rank`'s context, BORROWED (drmlt_node_context): film / chain inspection, kernel timing, render_pt. The node
+        """Rank `rank`'s context, BORROWED (drmlt_node_context): film / chain inspection, kernel timing, render_pt, render_bdpt. The node
         owns it; closing the returned object only forgets the handle."""
         return BorrowedContext(self, rank)
 

@@ -51,6 +51,20 @@ DEV void list_splat(const DParams &P, const float *list, float lum, float w) {
                  mk3(list[(size_t) (r0 + 2) * n] * sc, list[(size_t) (r0 + 3) * n] * sc, list[(size_t) (r0 + 4) * n] * sc));
     }
 }
+// ... with the plain factor sc, no division by the list luminance: an independent sample's contribution is f itself (k_render_bdpt)
+DEV void list_splat_scaled(const DParams &P, const float *list, float sc) {
+    const size_t n = P.n_chains_alloc;
+    const int meta = __float_as_int(list[(size_t) BL_META * n]);
+    if (meta & 1)
+        film_put(P, list[(size_t) BL_MAIN * n], list[(size_t) (BL_MAIN + 1) * n],
+                 mk3(list[(size_t) (BL_MAIN + 2) * n] * sc, list[(size_t) (BL_MAIN + 3) * n] * sc, list[(size_t) (BL_MAIN + 4) * n] * sc));
+    const int cnt = meta >> 1;
+    for (int k = 0; k < cnt; ++k) {
+        const int r0 = BL_MORE + 5 * k;
+        film_put(P, list[(size_t) r0 * n], list[(size_t) (r0 + 1) * n],
+                 mk3(list[(size_t) (r0 + 2) * n] * sc, list[(size_t) (r0 + 3) * n] * sc, list[(size_t) (r0 + 4) * n] * sc));
+    }
+}
 DEV void list_splat_const(const DParams &P, const float *list, f3 c) { // acceptance map: every splat position (:443-450)
     const size_t n = P.n_chains_alloc;
     const int meta = __float_as_int(list[(size_t) BL_META * n]);

@@ -39,6 +39,8 @@ void launch_eval_lists_bdpt(const DParams &P, const float *u, uint32_t n, uint32
 // algo=pssmlt over technique=bdpt (kernels_pssmlt_bdpt.hip); bootstrap, seed replay and evaluation are technique=bdpt's
 void launch_mutate_pssmlt_bdpt(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
 void launch_render_pt(const DParams &P, uint64_t n_samples, uint32_t stream, float scale, hipStream_t st);
+// independent bidirectional samples into a film (kernels_render_bdpt.hip)
+void launch_render_bdpt(const DParams &P, uint32_t n, float scale, size_t lds, hipStream_t st);
 // the direct-illumination pass (kernels_direct.hip)
 uint32_t direct_grid(const DirectJob &J, int width);
 void launch_render_direct(const DParams &P, const DirectJob &J, float *out, hipStream_t st);
@@ -819,6 +821,39 @@ int drmlt_render_pt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb)
     const uint64_t n = (uint64_t) spp * P.width * P.height;
     HIP_TRY(ctx, ensure_overflow(ctx, P, (size_t) 16384 * 64));
     launch_render_pt(P, n, 0u, 1.0f / (float) spp, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, film.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DRMLT_OK;
+}
+
+// Independent samples of sampleSplats(EBidirectional) into a film of its own: sample i is bootstrap sample i of stream 0 under
+// `seed` (drmlt_bootstrap_luminances reports its list luminance), every splat of its list goes through film_put with weight
+// 1 / spp. Scratch is the bootstrap's -- the workspace columns and list slot 1, which every mutation writes before it reads
+// (k_mutate_bdpt, k_mutate_pssmlt_bdpt: the first evaluation of a mutation targets slot 1; slot 2 is read only after its own
+// second stage wrote it) -- so the context's film, b, chain states, current lists (slot 0) and counters stay as they were.
+int drmlt_render_bdpt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb) {
+    if (!ctx || !out_rgb || spp == 0) return DRMLT_E_INVALID;
+    if (ctx->cfg.technique != DRMLT_TECH_BDPT)
+        return ctx->fail(DRMLT_E_INVALID, "drmlt_render_bdpt needs a context with technique=bdpt (its workspace, list rows and LDS plan)");
+    DParams P = ctx->P;
+    const uint64_t n = (uint64_t) spp * (uint64_t) P.width * (uint64_t) P.height;
+    if (n >= (1ull << 32))
+        return ctx->fail(DRMLT_E_INVALID, "render_bdpt: %u spp on %d x %d pixels are %llu samples, the sample address has 32 bits: "
+                                          "average several calls with different seeds", spp, P.width, P.height, (unsigned long long) n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf film;
+    const size_t bytes = (size_t) P.width * P.height * 3 * sizeof(float);
+    HIP_TRY(ctx, film.alloc(bytes));
+    HIP_TRY(ctx, hipMemsetAsync(film.p, 0, bytes, ctx->stream));
+    P.film = film.as<float>();
+    P.key0 = (uint32_t) seed; P.key1 = (uint32_t) (seed >> 32);
+    P.boot_stream = 0u;
+    P.importance = nullptr; // the image is of f itself
+    P.boot_weighted = 0;
+    P.debug &= ~128; // (the evaluation's cycle stamps go to the context's counters)
+    HIP_TRY(ctx, ensure_overflow(ctx, P, 2 * (size_t) P.n_chains_alloc)); // the grid's lanes: n_chains_alloc, as the bootstrap's
+    launch_render_bdpt(P, (uint32_t) n, 1.0f / (float) spp, ctx->plan.aux_lds, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out_rgb, film.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -326,6 +326,18 @@ int drmlt_kernel_time(drmlt_ctx *ctx, double *avg_ms, uint64_t *launches, int re
 /* Plain independent-sample path tracing of the same integrand
  * (test utility: equal-expectation reference for the MLT image). */
 int drmlt_render_pt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb);
+/* Independent samples of the bidirectional integrand into a film: for every sample one call of
+ * PathSampler::sampleSplats(EBidirectional) (pathsampler.cpp:321-527) on fresh uniform random numbers,
+ * its whole splat list -- the sensor-side splat and every light-image splat -- put through the scene's filter.
+ * out_rgb: W*H*3 floats, scaled so that the image's expectation is that of drmlt_develop.
+ * (Test utility: the equal-expectation reference of technique=bdpt and technique=mmlt.) The context must have
+ * technique=bdpt; the call follows its max_depth, rr_depth, no_direct_sampling, no_light_image and direct_samples
+ * (direct_samples > 0: depth <= 2 is excluded here as in the chains, render_bdpt + render_direct is the full image)
+ * and ignores the importance map and acceptance_map. Sample i of the spp*W*H samples reads the random numbers of
+ * bootstrap sample i of stream 0 under `seed` (drmlt_bootstrap_luminances). The context's film, b, chain states and
+ * counters are left as they were. DRMLT_E_INVALID: another technique, spp == 0, spp*W*H >= 2^32 (average several
+ * calls with different seeds), NULL pointers. */
+int drmlt_render_bdpt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb);
 
 /* The direct-illumination image that develop adds when directSamples > 0
  * (BidirectionalUtils::renderDirectComponent, src/libbidir/util.cpp:30-92, with
