@@ -100,6 +100,19 @@ class Splat(C.Structure):
 
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_uint64, C.c_void_p)
 
+LAYERS_WEIGHTED, LAYERS_UNWEIGHTED = 0, 1     # drmlt_render_bdpt_layers' mode
+BDPT_LAYERS_DEPTH_LIMIT = 32767               # above it the products below leave 32 bits: the library answers -1
+
+
+def bdpt_layer_count(max_depth):
+    """drmlt_bdpt_layer_count: layers (depth d, s) of a layered bidirectional film, 1 <= d <= max_depth, 0 <= s <= d + 1."""
+    return max_depth * (max_depth + 5) // 2 if 1 <= max_depth <= BDPT_LAYERS_DEPTH_LIMIT else -1
+
+
+def bdpt_layer_index(depth, s):
+    """drmlt_bdpt_layer_index: where layer (depth, s) lies among them (d = s + t - 1 edges); -1 outside the ranges."""
+    return (depth - 1) * (depth + 4) // 2 + s if 1 <= depth <= BDPT_LAYERS_DEPTH_LIMIT and 0 <= s <= depth + 1 else -1
+
 
 def make_config(**kw):
     """Defaults follow DRMLT's ctor (reference src/integrators/drmlt/drmlt.cpp:193-349)."""

@@ -30,6 +30,7 @@ ABI_SYMBOLS = (
     "drmlt_node_set_importance_map", "drmlt_node_device_count", "drmlt_node_context", "drmlt_node_last_error",
     "drmlt_node_destroy", "drmlt_bootstrap_luminances", "drmlt_seed_indices", "drmlt_comm_info", "drmlt_film_tile",
     "drmlt_render_direct", "drmlt_direct_split", "drmlt_node_render_direct", "drmlt_render_bdpt",
+    "drmlt_bdpt_layer_count", "drmlt_bdpt_layer_index", "drmlt_render_bdpt_layers",
 )
 
 
@@ -80,6 +81,9 @@ def load_library():
     L.drmlt_kernel_time.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
     L.drmlt_render_pt.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
     L.drmlt_render_bdpt.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+    L.drmlt_bdpt_layer_count.argtypes = [C.c_int32]
+    L.drmlt_bdpt_layer_index.argtypes = [C.c_int32, C.c_int32]
+    L.drmlt_render_bdpt_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_void_p]
     L.drmlt_chain_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.drmlt_last_error.restype = C.c_char_p
     L.drmlt_last_error.argtypes = [C.c_void_p]
@@ -304,6 +308,16 @@ class Context:
         (bootstrap_luminances); the context's film and chains are left alone."""
         out = np.empty((self.height, self.width, 3), dtype=np.float32)
         self._chk(self.L.drmlt_render_bdpt(self.h, spp, seed, out.ctypes.data))
+        return out
+
+    def render_bdpt_layers(self, spp, seed=1, weighted=True):
+        """render_bdpt(spp, seed)'s samples split by path length and strategy: (abi.bdpt_layer_count(max_depth), H, W, 3), layer
+        abi.bdpt_layer_index(d, s) holding the connections of s emitter-side and t = d + 1 - s sensor-side vertices. weighted:
+        with their MIS weights, the layers sum to render_bdpt's image; without, each layer is its strategy used alone.
+        `weighted` may also be one of abi.LAYERS_*: it is passed on as the mode."""
+        mode = weighted if type(weighted) is int else (abi.LAYERS_WEIGHTED if weighted else abi.LAYERS_UNWEIGHTED)
+        out = np.empty((abi.bdpt_layer_count(self.cfg.max_depth), self.height, self.width, 3), dtype=np.float32)
+        self._chk(self.L.drmlt_render_bdpt_layers(self.h, spp, seed, mode, out.ctypes.data))
         return out
 
     def render_direct(self, direct_samples=None, hide_emitters=False, seed=1, rows=None):

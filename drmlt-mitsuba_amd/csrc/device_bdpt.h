@@ -204,10 +204,23 @@ DEV int bdpt_row_cells(const DParams &P, int s, int nS, int &maxT) {
     return max(0, maxT - minT + 1);
 }
 
+// The per-cell sink: what eval_bdpt hands every connection (s, t) to, once per cell and round, by EVERY lane of the wave (a lane
+// without a cell of its own arrives with produced = false) -- a sink may use cross-lane operations. `px`, `py`: where the cell's
+// value lands on the film, the chain's sensor position for t >= 2 and the light-image position for t = 1 (pathsampler.cpp:514-519);
+// `value`: the cell's contribution as it enters the splat list, zero unless `produced`; `weight`: the sum of miWeight's squared
+// density ratios that `value` was divided by (1 for a cell that did not reach the weight); `c`: the lane of the cell's chain,
+// for the reads of whatever else belongs to it. The default does nothing and costs nothing: `enabled` keeps even the reads of
+// the film position out of the callers that do not ask (k_layers_bdpt does, kernels_layers_bdpt.hip).
+struct BdptNoSink {
+    static constexpr bool enabled = false;
+    DEV void operator()(int, int, float, float, f3, float, bool, uint32_t) const {}
+};
+
 // SamplerT: MSampler (the delayed-rejection chains, bootstrap, replay, evaluation points) or PssmltSampler3 (algo=pssmlt) -- what
 // the evaluation asks of it: lane, reset_caches(), select(segment), next(k), boot_k.
-template <int FEAT = 15, class TablesT, class SamplerT>
-DEV void eval_bdpt(const DParams &P, const TablesT &T, SamplerT &smp, bool active, uint32_t chain, uint32_t mis_row, float *list, BdptResult &R) {
+template <int FEAT = 15, class TablesT, class SamplerT, class SinkT = BdptNoSink>
+DEV void eval_bdpt(const DParams &P, const TablesT &T, SamplerT &smp, bool active, uint32_t chain, uint32_t mis_row, float *list, BdptResult &R,
+                   SinkT sink = SinkT()) {
     const uint32_t lane = smp.lane, n = P.n_chains_alloc;
     const int ME = P.max_depth, MS = P.max_depth + 1;
     const uint32_t NVS = (uint32_t) (ME + MS);
@@ -566,6 +579,7 @@ DEV void eval_bdpt(const DParams &P, const TablesT &T, SamplerT &smp, bool activ
         f3 value = mk3(0.f, 0.f, 0.f);
         float light_x = 0.f, light_y = 0.f;
         bool produced = false, traced = false;
+        [[maybe_unused]] float cell_weight = 1.f; // for the sink alone
         if (mine) do {
             BVert vs, vt;
             f3 thr_s = mk3(1.f, 1.f, 1.f), thr_t;
@@ -714,10 +728,15 @@ DEV void eval_bdpt(const DParams &P, const TablesT &T, SamplerT &smp, bool activ
                 }
             }
             value = value * (geo / (float) weight);
+            if constexpr (SinkT::enabled) cell_weight = (float) weight;
             if (t == 1 && !cam_sample_position(P, vs.p - vt.p, light_x, light_y)) { value = mk3(0.f, 0.f, 0.f); break; } // light image: its own splat (:514-516)
             produced = true;
         } while (0);
         if (!produced) value = mk3(0.f, 0.f, 0.f);
+        if constexpr (SinkT::enabled) { // the whole wave: the sensor position is the chain's, read from its lane
+            const float fx = __shfl(film_x, (int) c, 64), fy = __shfl(film_y, (int) c, 64);
+            sink(s, t, t == 1 ? light_x : fx, t == 1 ? light_y : fy, value, cell_weight, produced, c);
+        }
 
         // ---- a chain's results: light-image splats numbered in cell order, everything else summed over its segment
         const bool is_light = produced && t == 1;

@@ -5,6 +5,7 @@
 #include "device_types.h"
 #include "drmlt_ctx.h"
 #include "scene_prep.h"
+#include "bdpt_layers.h"
 
 #include <hip/hip_runtime.h>
 
@@ -41,6 +42,8 @@ void launch_mutate_pssmlt_bdpt(const ChainPlan &plan, const DParams &P, uint32_t
 void launch_render_pt(const DParams &P, uint64_t n_samples, uint32_t stream, float scale, hipStream_t st);
 // independent bidirectional samples into a film (kernels_render_bdpt.hip)
 void launch_render_bdpt(const DParams &P, uint32_t n, float scale, size_t lds, hipStream_t st);
+// ... split by path length and strategy into a layered film (kernels_layers_bdpt.hip)
+void launch_layers_bdpt(const DParams &P, uint32_t n, float scale, float *layers, int unweighted, size_t lds, hipStream_t st);
 // the direct-illumination pass (kernels_direct.hip)
 uint32_t direct_grid(const DirectJob &J, int width);
 void launch_render_direct(const DParams &P, const DirectJob &J, float *out, hipStream_t st);
@@ -856,6 +859,48 @@ int drmlt_render_bdpt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rg
     launch_render_bdpt(P, (uint32_t) n, 1.0f / (float) spp, ctx->plan.aux_lds, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out_rgb, film.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DRMLT_OK;
+}
+
+int drmlt_bdpt_layer_count(int32_t max_depth) { return bdpt_layer_count(max_depth); }
+int drmlt_bdpt_layer_index(int32_t depth, int32_t s) { return bdpt_layer_index(depth, s); }
+
+// drmlt_render_bdpt's samples, cell by cell: every connection (s, t) that produced goes into layer (d = s + t - 1, s) of a layered
+// film, which is an allocation of this call. Refusals, scratch and what is left alone are drmlt_render_bdpt's; the splat lists the
+// evaluation writes into slot 1 on the way are not read.
+int drmlt_render_bdpt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t mode, float *out_layers) {
+    if (!ctx || !out_layers) return DRMLT_E_INVALID;
+    if (spp == 0) return ctx->fail(DRMLT_E_INVALID, "render_bdpt_layers: spp is 0, a render takes at least one sample per pixel");
+    if (ctx->cfg.technique != DRMLT_TECH_BDPT)
+        return ctx->fail(DRMLT_E_INVALID, "drmlt_render_bdpt needs a context with technique=bdpt (its workspace, list rows and LDS plan)");
+    if (mode != DRMLT_LAYERS_WEIGHTED && mode != DRMLT_LAYERS_UNWEIGHTED)
+        return ctx->fail(DRMLT_E_INVALID, "render_bdpt_layers: unknown mode %d (DRMLT_LAYERS_WEIGHTED = %d, DRMLT_LAYERS_UNWEIGHTED = %d)",
+                         (int) mode, (int) DRMLT_LAYERS_WEIGHTED, (int) DRMLT_LAYERS_UNWEIGHTED);
+    DParams P = ctx->P;
+    const uint64_t n = (uint64_t) spp * (uint64_t) P.width * (uint64_t) P.height;
+    if (n >= (1ull << 32))
+        return ctx->fail(DRMLT_E_INVALID, "render_bdpt: %u spp on %d x %d pixels are %llu samples, the sample address has 32 bits: "
+                                          "average several calls with different seeds", spp, P.width, P.height, (unsigned long long) n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf layers;
+    const size_t bytes = (size_t) bdpt_layer_count(P.max_depth) * P.width * P.height * 3 * sizeof(float);
+    if (layers.alloc(bytes) != hipSuccess) {
+        (void) hipGetLastError(); // (the failed allocation is reported here, not by the next call that asks for the last error)
+        return ctx->fail(DRMLT_E_DEVICE, "render_bdpt_layers: cannot allocate the layered film, %llu bytes (%d layers of %d x %d pixels)",
+                         (unsigned long long) bytes, bdpt_layer_count(P.max_depth), P.width, P.height);
+    }
+    HIP_TRY(ctx, hipMemsetAsync(layers.p, 0, bytes, ctx->stream));
+    P.film = nullptr; // nothing here writes a film but the sink
+    P.key0 = (uint32_t) seed; P.key1 = (uint32_t) (seed >> 32);
+    P.boot_stream = 0u;
+    P.importance = nullptr; // the layers are of f itself
+    P.boot_weighted = 0;
+    P.debug &= ~128; // (the evaluation's cycle stamps go to the context's counters)
+    HIP_TRY(ctx, ensure_overflow(ctx, P, 2 * (size_t) P.n_chains_alloc)); // the grid's lanes, as drmlt_render_bdpt
+    launch_layers_bdpt(P, (uint32_t) n, 1.0f / (float) spp, layers.as<float>(), mode == DRMLT_LAYERS_UNWEIGHTED, ctx->plan.aux_lds, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out_layers, layers.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return DRMLT_OK;
 }

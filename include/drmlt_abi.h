@@ -338,6 +338,24 @@ int drmlt_render_pt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb)
  * counters are left as they were. DRMLT_E_INVALID: another technique, spp == 0, spp*W*H >= 2^32 (average several
  * calls with different seeds), NULL pointers. */
 int drmlt_render_bdpt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb);
+/* The same samples split by path length and strategy: Veach's "pyramid" of the bidirectional estimate. A layer is a
+ * pair (depth d, s), d = s + t - 1 the number of edges of a path made by connecting s emitter-side to t sensor-side
+ * vertices (pathsampler.cpp:369-521): 1 <= d <= max_depth, 0 <= s <= d + 1. drmlt_bdpt_layer_index(d, s) =
+ * (d - 1)(d + 4)/2 + s, drmlt_bdpt_layer_count(D) = D(D + 5)/2; both are plain arithmetic, need no device and give -1
+ * outside these ranges. The t = 0 layers exist for regular indexing; a pinhole sensor cannot be hit, they stay zero.
+ * out_layers: count(max_depth)*H*W*3 floats, layer after layer. Every connection of sample i of
+ * drmlt_render_bdpt(ctx, spp, seed, ...) -- same random numbers, scale, filter and options -- goes to its layer, at the
+ * sample's sensor position for t >= 2 and at the light-image position for t = 1 (pathsampler.cpp:514-519).
+ * DRMLT_LAYERS_WEIGHTED: the connection's value as it enters the splat list, multiplied by its MIS weight
+ * (Path::miWeight, path.cpp:763-1028); the layers sum to drmlt_render_bdpt's image. DRMLT_LAYERS_UNWEIGHTED: the value
+ * without that weight; a layer is then strategy (s, t) used alone, an estimator in its own right of the depth-d light
+ * wherever the strategy can sample it. The layered film is a device allocation of the call (DRMLT_E_DEVICE with the
+ * byte count if it cannot be had); the context is left as drmlt_render_bdpt leaves it. DRMLT_E_INVALID: what
+ * drmlt_render_bdpt refuses, and an unknown mode. */
+enum { DRMLT_LAYERS_WEIGHTED = 0, DRMLT_LAYERS_UNWEIGHTED = 1 };
+int drmlt_bdpt_layer_count(int32_t max_depth);
+int drmlt_bdpt_layer_index(int32_t depth, int32_t s);
+int drmlt_render_bdpt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t mode, float *out_layers);
 
 /* The direct-illumination image that develop adds when directSamples > 0
  * (BidirectionalUtils::renderDirectComponent, src/libbidir/util.cpp:30-92, with
