@@ -1222,7 +1222,25 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
 // same. A lane whose path ends may compute garbage (NaN, inf) in what it does not use; none of it reaches `ps` or `sr`:
 // radiance, dimensions and rays are selected, the shadow ray is written only when it is handed over, and the vertex
 // and bounce fields only when the path goes on (a path that ends, or waits for its shadow ray, never reads them again).
-template <class SamplerT, class TablesT>
+// MASKED = false (k_mutate_w2): that last sentence is used instead of guarded against. Only what the caller reads of a path that
+// has ended stays selected -- sr.valid, ps.Li, ps.k, ps.nrays, ps.shadow_pending, ps.phase -- and every other field is written
+// on every lane that steps, garbage included: the two `if` blocks cost a saved exec mask and a run of masked v_mov each, per loop
+// iteration. What is written without its condition, who could read it afterwards, and where it is set anew:
+//   ps.nee                         read by the next step under ps.shadow_pending only (selected here; path_init clears it)
+//   ps.thr, eta, depth, direct_on,
+//   non_specular, has_bounce       path_init
+//   ps.n, bpdf, bweight, beta_eta,
+//   bdelta                         read by the next step under ps.has_bounce only (path_init clears it); the step that follows
+//                                  path_begin computes with stale values there in the masked form as well, and selects them away
+//   ps.wi, s, bsdf                 written for path_step's sake; this routine reads none of them
+//   ps.o, d, tmin, tmax            path_begin; what a ray pass finds is read only after a PH_CLOSEST, which is selected (k_mutate_w2
+//                                  runs the pass on every lane: one without a ray traces this garbage and nobody reads its hit)
+//   sr.o, d, tmin, tmax            the helper lane's hit counts only under sr.valid (selected)
+// Between a path's end and its path_init the lane is parked: mh_decide reads ps.px, ps.py, ps.Li, ps.nrays (and ps.k outside the
+// orbital rule), the hand-off passes sr on, and nothing else looks at `ps`. A PH_FLUSH step (the path ended with its last shadow
+// ray pending) runs this routine once more: it reads ps.Li, ps.nee, ps.shadow_pending of what was written, all three as the masked
+// form leaves them, and selects everything else away (live = false).
+template <class SamplerT, class TablesT, bool MASKED = true>
 DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, SamplerT &smp, const Hit &hit, bool shadow_clear,
                            ShadowRay &sr) {
     static_assert(draws_batched<SamplerT>::value, "the five draws are requested together");
@@ -1309,14 +1327,14 @@ DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, Sa
     ps.nrays += (nee ? 1u : 0u) + (bounce ? 1u : 0u);
     ps.shadow_pending = nee;
     ps.phase = bounce ? PH_CLOSEST : (nee ? PH_FLUSH : PH_DONE);
-    if (nee) {
+    if (!MASKED || nee) {
         ps.nee = c;
         sr.o = p; sr.d = dd;
         sr.tmin = ray_eps_shadow(p);
         sr.tmax = dist * (1.f - SHADOW_EPSILON_F);
-        sr.valid = true;
+        sr.valid = MASKED || nee;
     }
-    if (bounce) {
+    if (!MASKED || bounce) {
         ps.thr = thr; ps.eta = eta; ps.depth = depth; ps.direct_on = direct_on;
         ps.wi = wi;
         ps.o = p; ps.n = n; ps.s = s;

@@ -909,10 +909,24 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(
 //                           pass reads its record pointers and counts as k_mutate_v4 does (holding them measured slower).
 //   -DW2_TWO_PHILOX         off: a fill item computes its counter and tag per lane and calls Philox ONCE; only the tail differs
 //                           (row_fill_first_drawn for a proposal block, four writes for a coin block).
+//   -DW2_MASKED_STEP        off: the step writes the vertex, the bounce, ps.nee and the shadow ray on every lane that steps and selects
+//                           only what a path that has ended is still read for (path_step_diffuse<.., MASKED = false>, device_path.h,
+//                           lists each field and where it is set anew); the twin's two masked copy-back blocks are gone.
+//   -DW2_COPIED_HANDOFF     off: the shadow ray reaches the helper lanes in ONE v_permlane32_swap per value (lower_keeps: a chain lane
+//                           keeps its own ray, its helper receives the shadow ray) in place of a broadcast from the lower half and
+//                           a block of masked moves on the helpers.
+//   -DW2_MASKED_TRACE       off: when any lane has a ray the WHOLE wave runs the ray pass (a wave-uniform test, no saved exec mask and
+//                           no masked merge of the hit), and the shadow ray of a lane that does not step is left undefined instead
+//                           of being set to zeros and copies. The ray loops read memory through scalar loads only, so a lane without
+//                           a ray computes garbage and touches nothing; `h` is read by lanes that traced, and by a PH_FLUSH step, which
+//                           uses hit.prim -- a record's index or -1 -- for an LDS address and selects everything else away.
 // Not here: the step's component reads issued ahead of the ray pass, and components and shading record requested in one batch
 // (both built and measured: no gain and a loss, section 7a). The splat path keeps
 // film_put_channel's debug test (DRMLT_DEBUG bit 1 must go on working; one scalar compare per flushed splat).
 // stats[16] counts the waves that ran it (no build without stamps writes that slot; drmlt_stats_get prints it under DRMLT_VERBOSE).
+// the hand-off in one v_permlane32_swap per value: lane i < 32 keeps `keep`, lane 32 + i receives lane i's `give`
+DEV unsigned lower_keeps_u(unsigned keep, unsigned give) { return __builtin_amdgcn_permlane32_swap(keep, give, false, false)[0]; }
+DEV float lower_keeps(float keep, float give) { return __uint_as_float(lower_keeps_u(__float_as_uint(keep), __float_as_uint(give))); }
 template <class T> DEV void hold_v(T &x) { asm volatile("" : "+v"(x)); }
 DEV uint32_t wave_uniform(uint32_t v) { return (uint32_t) __builtin_amdgcn_readfirstlane((int) v); }
 template <class T> DEV T *uniform_ptr(uint32_t lo, uint32_t hi) { return reinterpret_cast<T *>((uintptr_t) wave_uniform(lo) | ((uintptr_t) wave_uniform(hi) << 32)); }
@@ -1185,13 +1199,22 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_
         __builtin_amdgcn_s_setprio(0);
         {
             SECTION_PARAMS(Pt);
+#ifndef W2_MASKED_TRACE
+            if (__ballot(tracing)) h = trace<0>(Pt, ps.o, ps.d, ps.tmin, ps.tmax, helper); // every lane, whatever its ray: only lanes that traced read `h`
+#else
             if (tracing) h = trace<0>(Pt, ps.o, ps.d, ps.tmin, ps.tmax, helper);
+#endif
         }
         __builtin_amdgcn_s_setprio(3);
         const unsigned occluded = from_upper_u((helper_has_ray && h.prim >= 0) ? 1u : 0u);
         helper_has_ray = false;
         ShadowRay sr;
+#ifndef W2_MASKED_TRACE
+        asm volatile("" : "=v"(sr.d.x), "=v"(sr.d.y), "=v"(sr.d.z), "=v"(sr.tmin), "=v"(sr.tmax)); // whatever the registers hold: read under sr.valid only
+        sr.o = ps.o; sr.valid = false;
+#else
         sr.o = ps.o; sr.d = ps.d; sr.tmin = 0.f; sr.tmax = 0.f; sr.valid = false;
+#endif
         {
             // no scalar load at the head of the step; its LDS reads still leave in three dependent trips (components, shading record, BSDF)
             W2_SECTION(Cs);
@@ -1201,10 +1224,20 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_
                 DParams Vs{}; // what path_step_diffuse reads of the block
                 Vs.eff_dim = Cs.eff_dim; Vs.rr_depth = Cs.rr_depth; Vs.max_depth = Cs.max_depth;
                 const LdsTables LT{Cs.shade_off, Cs.bsdf_off, 0u}; // (the emitter table is not read: HeldLightTables)
+#ifndef W2_MASKED_STEP
+                path_step_diffuse<RowSampler, HeldLightTables, false>(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
+#else
                 path_step_diffuse(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
+#endif
             }
         }
         // hand the shadow ray of this vertex to the helper lane
+#ifndef W2_COPIED_HANDOFF
+        ps.o.x = lower_keeps(ps.o.x, sr.o.x); ps.o.y = lower_keeps(ps.o.y, sr.o.y); ps.o.z = lower_keeps(ps.o.z, sr.o.z);
+        ps.d.x = lower_keeps(ps.d.x, sr.d.x); ps.d.y = lower_keeps(ps.d.y, sr.d.y); ps.d.z = lower_keeps(ps.d.z, sr.d.z);
+        ps.tmin = lower_keeps(ps.tmin, sr.tmin); ps.tmax = lower_keeps(ps.tmax, sr.tmax);
+        helper_has_ray = lower_keeps_u(0u, sr.valid ? 1u : 0u) != 0u; // (a chain lane keeps the `false` set above)
+#else
         const float ox = from_lower(sr.o.x), oy = from_lower(sr.o.y), oz = from_lower(sr.o.z);
         const float dx = from_lower(sr.d.x), dy = from_lower(sr.d.y), dz = from_lower(sr.d.z);
         const float t0 = from_lower(sr.tmin), t1 = from_lower(sr.tmax);
@@ -1213,6 +1246,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_
             ps.o = mk3(ox, oy, oz); ps.d = mk3(dx, dy, dz); ps.tmin = t0; ps.tmax = t1;
             helper_has_ray = vf != 0.f;
         }
+#endif
     }
     // the epilogue of k_mutate_v4, on its own copy of the block
     SECTION_PARAMS(Pe);

@@ -3,9 +3,10 @@
 #   cd drmlt-mitsuba_amd/csrc && make -B OUT=../variants/libD.so DEVFLAGS="<the Makefile's DEVFLAGS> -mllvm -amdgpu-sched-strategy=max-ilp"
 # (drmlt-mitsuba_amd/variants/ is git-ignored; DRMLT_LIBRARY makes the binding load another build of the same ABI).
 # k_mutate_w2's ingredient switches (kernels.hip) are source switches, built the same way through CXXFLAGS, e.g.
-#   make -B OUT=../variants/libH.so CXXFLAGS="<the Makefile's CXXFLAGS> -DW2_NO_HELD_CONSTANTS"   (likewise -DW2_SCALARS_LOADED, -DW2_TWO_PHILOX)
+#   make -B OUT=../variants/libH.so CXXFLAGS="<the Makefile's CXXFLAGS> -DW2_NO_HELD_CONSTANTS"   (likewise -DW2_SCALARS_LOADED, -DW2_TWO_PHILOX,
+#   -DW2_MASKED_STEP, -DW2_COPIED_HANDOFF, -DW2_MASKED_TRACE)
 # and run with VARIANTS="A H ..." here or in codegen_ab_bench.sh (config 2). Nothing else builds them: after an edit to k_mutate_w2,
-# build all three once (as of their commit 135 / 187 / 198 VGPRs against the default build's 199, no spill) and run tests/test_gpu_w2.py under DRMLT_LIBRARY.
+# build all six once (no spill in any) and run tests/test_gpu_w2.py and tests/test_gpu_w2_step.py under DRMLT_LIBRARY.
 # Round 2: -amdgpu-early-ifcvt, -amdgpu-sched-strategy=max-ilp and raised SimplifyCFG phi-folding thresholds all stay within
 # +-1 % of the default build on config 2, config 3 and the soup.
 for v in ${VARIANTS:-A B D E}; do
