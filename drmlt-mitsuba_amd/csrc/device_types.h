@@ -78,7 +78,8 @@ struct DBsdf {
 struct DEmitter {
     float radiance[3];
     int32_t prim;
-    float cdf_lo, cdf_hi; // DiscreteDistribution entries (normalised)
+    float cdf_lo, cdf_hi; // DiscreteDistribution entries (normalised). cdf_lo is -FLT_MIN, not 0, for the first emitter of non-zero weight
+                          // behind leading emitters of weight 0 (scene_prep.h): every pick loop takes the last i with cdf_lo(i) < sx
     float pad[2];
 };
 

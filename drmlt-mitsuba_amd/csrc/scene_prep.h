@@ -14,6 +14,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -52,13 +53,22 @@ inline bool invert3x4(const double *m, double *o) {
 // ConstantBackgroundEmitter::createShape (constant.cpp:67-92): the bounding sphere of the scene's box, its radius times 1.5 (at least
 // Epsilon). The box is the geometry's (the kd-tree's) expanded by the sensor's position: DRMLT calls Scene::initializeBidirectional
 // (scene.cpp:396-423), which builds it before any emitter's shape. AABB::getBSphere: the box's centre, the distance to its max
-// corner. Only the length of the light sample's shadow ray depends on it.
+// corner. The kd-tree's box is the geometry's tight one enlarged by MTS_KD_AABB_EPSILON = 1e-3 of its extent plus 1e-3, the upper
+// side from the already lowered minimum (gkdtree.h:1213-1220, in Float). Only the length of the light sample's shadow ray
+// depends on it.
 inline void scene_bsphere(const drmlt_scene &s, const std::vector<PrimBounds> &bounds, float centre[3], float &radius) {
     const double cam[3] = {s.camera.to_world[3], s.camera.to_world[7], s.camera.to_world[11]};
     double lo[3], hi[3], r2 = 0;
     for (int k = 0; k < 3; ++k) {
         lo[k] = hi[k] = cam[k];
-        for (const PrimBounds &b : bounds) { lo[k] = std::min(lo[k], (double) b.lo[k]); hi[k] = std::max(hi[k], (double) b.hi[k]); }
+        if (!bounds.empty()) {
+            float tlo = bounds[0].lo[k], thi = bounds[0].hi[k];
+            for (const PrimBounds &b : bounds) { tlo = std::min(tlo, b.lo[k]); thi = std::max(thi, b.hi[k]); }
+            const float eps = 1e-3f;
+            tlo -= (thi - tlo) * eps + eps;
+            thi += (thi - tlo) * eps + eps;
+            lo[k] = std::min(lo[k], (double) tlo); hi[k] = std::max(hi[k], (double) thi);
+        }
         const double c = 0.5 * (lo[k] + hi[k]);
         centre[k] = (float) c;
         r2 += (hi[k] - c) * (hi[k] - c);
@@ -333,6 +343,13 @@ inline std::string build_scene(const drmlt_scene &s, const Knobs &K, PreparedSce
             out.shade.push_back(sh);
         }
         e.cdf_lo = raw[i]; e.cdf_hi = raw[i + 1];
+        // Every pick loop of the device (path_step, direct_emitter_sample, device_bidir.h, device_bdpt.h) takes the last emitter whose
+        // cdf_lo lies below the sample. Behind leading emitters of
+        // weight 0 the first one that can be sampled starts at 0 as they do, and a sample of exactly 0 would stay with entry 0 and
+        // its probability 0, where DiscreteDistribution::sample steps over zero-width entries (pmf.h:124-139). The smallest normal
+        // number below 0 sends that sample to it; cdf_hi - cdf_lo and the reused sample (sx - cdf_lo) / (cdf_hi - cdf_lo) keep their
+        // values but for 1e-38.
+        if (i > 0 && raw[i] == 0.f && raw[i + 1] > 0.f) e.cdf_lo = -std::numeric_limits<float>::min();
         out.emitters.push_back(e);
     }
     return "";

@@ -363,6 +363,34 @@ def bsdf_probe(precision, ggx, alpha, eta, k, wi, wo=None, m=None, sxy=None, spe
                 eval_at_wo=out[:, 22:25])
 
 
+LIGHT_PROBE_IN, LIGHT_PROBE_COLS = 12, 19
+
+
+def light_probe(precision, scene_data, ref, ref_n, sxy=None, emitter=-1, point=None, point_n=None):
+    """The light-sampling routines of the oracle's scene, row by row, in float (32) or double (64) arithmetic.
+    sxy given: Scene::sampleEmitterDirect without its visibility test (emitter < 0), or shapeSampleDirect / envSampleDirect of
+    emitter `emitter` alone. point and point_n given: pdfEmitterDirect and pdfEmitterDirectArea of that point on `emitter`."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    ref = f(ref)
+    n = len(ref)
+    rows = np.zeros((n, LIGHT_PROBE_IN))
+    rows[:, 0:3], rows[:, 3:6] = ref, f(ref_n)
+    if sxy is not None:
+        rows[:, 6:8] = f(sxy)
+    else:
+        rows[:, 6:9], rows[:, 9:12] = f(point), f(point_n)
+    out = np.zeros((n, LIGHT_PROBE_COLS))
+    info = np.zeros(5 + len(scene_data.emitters))
+    L = lib()
+    L.oracle_light_probe.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    scene = scene_data.struct()
+    rc = L.oracle_light_probe(precision, C.addressof(scene), 0 if sxy is not None else 1, int(emitter), n, rows.ctypes.data, out.ctypes.data, info.ctypes.data)
+    if rc != 0:
+        raise OracleError("light_probe: " + ("precision must be 32 or 64" if rc == -1 else "the scene does not load, or the emitter has no such entry"))
+    return dict(emitter=out[:, 0].astype(np.int64), em_pdf=out[:, 1], sx=out[:, 2], d=out[:, 3:6], dist=out[:, 6], n=out[:, 7:10], pdf=out[:, 10],
+                value=out[:, 11:14], pdf_direct=out[:, 14], pdf_area=out[:, 15], p=out[:, 16:19], env_center=info[0:3], env_radius=info[3], cdf=info[4:])
+
+
 def _elementwise(name, precision, args, cols, *ints):
     args = [np.ascontiguousarray(a, dtype=np.float64) for a in args]
     n = len(args[0])

@@ -719,7 +719,70 @@ template <typename F> static void fresnelProbe(int kind, uint32_t n, const doubl
     }
 }
 
+// The light-sampling routines of Scene<F>, row by row, in float or double arithmetic over the caller's scene. A row of `in`
+// (LIGHT_PROBE_IN doubles) holds ref 0-2, refN 3-5 and either (sx, sy) 6-7 (mode 0) or a point on the emitter and its normal
+// 6-11 (mode 1). mode 0, emitter < 0: sampleEmitterDirect(testVisibility = false); emitter >= 0: shapeSampleDirect /
+// envSampleDirect of that emitter alone (sx as given, no facing test). mode 1: the densities with which direct sampling from
+// ref produces the given point (d and dist follow from the two positions, as PathVertex::evalPdfDirect has them).
+// A row of `out` (LIGHT_PROBE_COLS doubles): 0 the emitter picked, 1 its probability, 2 the reused sx, 3-5 d, 6 dist, 7-9 n,
+// 10 pdf, 11-13 value, 14 pdfEmitterDirect (forced shape: shapePdfDirect), 15 pdfEmitterDirectArea (area emitters), 16-18 p.
+// info: envCenter, envRadius, then the n + 1 entries of the emitter CDF.
+enum { LIGHT_PROBE_IN = 12, LIGHT_PROBE_COLS = 19 };
+template <typename F> static int lightProbe(const drmlt_scene *s, int mode, int emitter, uint32_t n, const double *in, double *out, double *info) {
+    Scene<F> scene;
+    if (!scene.load(*s).empty() || emitter >= (int) scene.emitters.size()) return -2;
+    if (mode == 1 && (emitter < 0 || scene.emitters[emitter].type != DRMLT_EMITTER_AREA)) return -2;
+    auto v3 = [](const double *p) { return V3<F>((F) p[0], (F) p[1], (F) p[2]); };
+    auto put3 = [](double *o, const V3<F> &v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; };
+    for (int a = 0; a < 3; ++a) info[a] = scene.envCenter[a];
+    info[3] = scene.envRadius;
+    for (size_t i = 0; i < scene.emitterCdf.size(); ++i) info[4 + i] = scene.emitterCdf[i];
+    for (uint32_t i = 0; i < n; ++i) {
+        const double *x = in + (size_t) LIGHT_PROBE_IN * i;
+        double *o = out + (size_t) LIGHT_PROBE_COLS * i;
+        typename Scene<F>::DirectSample dRec;
+        dRec.ref = v3(x); dRec.refN = v3(x + 3);
+        V3<F> value(0);
+        if (mode == 1) {
+            dRec.p = v3(x + 6); dRec.n = v3(x + 9);
+            dRec.d = dRec.p - dRec.ref;
+            dRec.dist = dRec.d.length();
+            dRec.d /= dRec.dist;
+            dRec.emitter = emitter;
+            o[0] = emitter;
+            o[14] = scene.pdfEmitterDirect(dRec); o[15] = scene.pdfEmitterDirectArea(dRec);
+        } else if (emitter < 0) {
+            F sx = (F) x[6], emPdf = 0;
+            o[0] = (double) scene.sampleEmitterIndex(sx, emPdf); o[1] = emPdf; o[2] = sx;
+            value = scene.sampleEmitterDirect(dRec, (F) x[6], (F) x[7], nullptr, false);
+            if (dRec.pdf != 0) {
+                o[14] = scene.pdfEmitterDirect(dRec);
+                if (scene.emitters[dRec.emitter].type == DRMLT_EMITTER_AREA) o[15] = scene.pdfEmitterDirectArea(dRec);
+            }
+        } else {
+            const Emitter<F> &em = scene.emitters[emitter];
+            dRec.emitter = emitter;
+            o[0] = emitter; o[1] = scene.emitterCdf[emitter + 1] - scene.emitterCdf[emitter]; o[2] = x[6];
+            if (em.type == DRMLT_EMITTER_CONSTANT) value = scene.envSampleDirect(em, dRec, (F) x[6], (F) x[7]);
+            else if (em.type == DRMLT_EMITTER_AREA) {
+                scene.shapeSampleDirect(scene.shapes[em.shape], dRec, (F) x[6], (F) x[7]);
+                o[14] = scene.shapePdfDirect(scene.shapes[em.shape], dRec); o[15] = scene.pdfEmitterDirectArea(dRec);
+            } else value = scene.pointSampleDirect(em, dRec);
+        }
+        put3(o + 3, dRec.d); o[6] = dRec.dist; put3(o + 7, dRec.n); o[10] = dRec.pdf; put3(o + 11, value); put3(o + 16, dRec.p);
+    }
+    return 0;
+}
+
 extern "C" {
+
+int oracle_light_probe(int precision, const drmlt_scene *scene, int mode, int emitter, uint32_t n, const double *in, double *out, double *info) {
+    try {
+        if (precision == 32) return lightProbe<float>(scene, mode, emitter, n, in, out, info);
+        if (precision == 64) return lightProbe<double>(scene, mode, emitter, n, in, out, info);
+    } catch (const std::exception &) { return -2; }
+    return -1;
+}
 
 int oracle_bsdf_probe(int precision, int ggx, double alpha, const double *eta, const double *k, const double *specular_reflectance, uint32_t n,
                       const double *wi, const double *wo_in, const double *m_in, const double *sxy, double *out) {

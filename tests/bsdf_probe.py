@@ -39,14 +39,15 @@ def flags(unit):
     return _make_var("CXXFLAGS") + _make_var("DEVFLAGS") + _make_var("FLAGS_" + unit)
 
 
-def build(out_dir, unit):
-    """-> (executable, the compiler's kernel-resource-usage remarks)."""
-    exe = os.path.join(str(out_dir), "bsdf_probe_" + unit)
+def build(out_dir, unit, src=SRC):
+    """-> (executable, the compiler's kernel-resource-usage remarks). src: the probe program (tests/light_probe.py has another)."""
+    name = os.path.splitext(os.path.basename(src))[0]
+    exe = os.path.join(str(out_dir), name + "_" + unit)
     hipcc = _make_var("HIPCC")[0]
     r = subprocess.run([hipcc, "--offload-arch=" + _make_var("ARCH")[0], *flags(unit), "-I", CSRC,
-                        "-Rpass-analysis=kernel-resource-usage", "-o", exe, SRC], capture_output=True, text=True)
+                        "-Rpass-analysis=kernel-resource-usage", "-o", exe, src], capture_output=True, text=True)
     if r.returncode != 0:
-        raise RuntimeError("bsdf_probe does not compile (%s):\n%s" % (unit, r.stderr[-4000:]))
+        raise RuntimeError("%s does not compile (%s):\n%s" % (name, unit, r.stderr[-4000:]))
     return exe, r.stderr
 
 
