@@ -920,6 +920,10 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(
 //                           of being set to zeros and copies. The ray loops read memory through scalar loads only, so a lane without
 //                           a ray computes garbage and touches nothing; `h` is read by lanes that traced, and by a PH_FLUSH step, which
 //                           uses hit.prim -- a record's index or -1 -- for an LDS address and selects everything else away.
+//   -DW2_SHARED_FLUSH       off: the film flush is w2_flush (below): the box filter and the tabulated filters in separate loop nests,
+//                           the table read from LDS, so that no wait inside a flush names vmcnt and the film's no-return atomics
+//                           are never waited for (+1.0 % with the box filter, -0.9 % with the Gaussian, where the atomics are
+//                           the bound). With the switch the three flush sites call v4_flush as the twin does.
 // Not here: the step's component reads issued ahead of the ray pass, and components and shading record requested in one batch
 // (both built and measured: no gain and a loss, section 7a). The splat path keeps
 // film_put_channel's debug test (DRMLT_DEBUG bit 1 must go on working; one scalar compare per flushed splat).
@@ -975,6 +979,58 @@ DEV RowSamplerT<RULE_ORBITAL> w2_sampler(uint32_t key0, uint32_t key1) { // the 
     s.x_off = s.y_off = s.xyz = 0u;
     return s;
 }
+// k_mutate_w2's film flush: film_put_channel and v4_flush with the box filter and the tabulated filters in two loop nests of their
+// own, chosen once per flush by a wave-uniform test. Same passes, lanes, addresses, values and order of the atomics. In the shared
+// routine the weight is `box ? constant : P.filter_lut[i]`; the compiler merges the arms, and the wait in front of the table value
+// stands on the box path too, where no load was issued: there it waits for the no-return atomics of the previous pass, which count
+// in the same vmcnt. Here the box nest reads no memory at all, so nothing in it waits for an atomic, and the tabulated nest reads
+// its table from LDS (lgkmcnt): `lut` is the wave's list area (V4Lds::list_off, the 32 words v4_layout leaves between the coins
+// and the queue), staged anew by every flush because the fill passes of every bookkeeping branch overwrite it. The area is free
+// whenever a flush runs: the branch's flush precedes the list writes of the same call and nothing between the staging and the last
+// table read writes LDS but the flush itself (it reads the queue rows only); the epilogue's flushes run after the loop. One wave
+// per workgroup: the ds_write and the ds_reads of other lanes need no barrier (as lds_list's).
+template <bool BOX> DEV void w2_film_put_channel(const DParams &P, const float *lut, float px, float py, float v, int ch) {
+    if (P.debug & 1) return;
+    float posx = px - 0.5f, posy = py - 0.5f;
+    int minx = max((int) ceilf(posx - P.filter_radius), 0), miny = max((int) ceilf(posy - P.filter_radius), 0);
+    int maxx = min((int) floorf(posx + P.filter_radius), P.width - 1), maxy = min((int) floorf(posy + P.filter_radius), P.height - 1);
+    for (int y = miny; y <= maxy; ++y) {
+        const int iy = min((int) fabsf(((float) y - posy) * P.filter_scale), 31);
+        float wy = BOX ? (iy < 31 ? P.box_weight : 0.f) : lut[iy];
+        for (int x = minx; x <= maxx; ++x) {
+            const int ix = min((int) fabsf(((float) x - posx) * P.filter_scale), 31);
+            float w = (BOX ? (ix < 31 ? P.box_weight : 0.f) : lut[ix]) * wy;
+            atomic_add_global_f32(P.film + ((size_t) y * P.width + x) * 3 + ch, w * v);
+        }
+    }
+}
+template <bool BOX> DEV void w2_flush_passes(const DParams &P, const V4Lds &L, const float *lut, uint32_t qn, uint32_t lane) {
+    const uint32_t s = lane / 3u, ch = lane - 3u * s;
+    for (uint32_t base = 0u; base < qn; base += 21u) {
+        const uint32_t e = base + s;
+        if (e < qn && s < 21u) {
+            const float *q = &lds_x[L.q_off + e];
+            w2_film_put_channel<BOX>(P, lut, q[0], q[L.qcap], q[(2u + ch) * L.qcap], (int) ch);
+        }
+    }
+}
+DEV void w2_flush(const DParams &P, const V4Lds &L, uint32_t &qn, uint32_t lane) {
+    float *const lut = &lds_x[L.list_off];
+    if (P.box_weight > 0.f) w2_flush_passes<true>(P, L, lut, qn, lane);
+    else if (qn) {
+        // the one vector-memory load of a flush, and its one wait. The wait also covers whatever atomics the previous flush left
+        // outstanding: those are about six bookkeeping calls old.
+        if (lane < 32u) lut[lane] = P.filter_lut[lane];
+        w2_flush_passes<false>(P, L, lut, qn, lane);
+    }
+    qn = 0u;
+}
+#ifndef W2_SHARED_FLUSH
+#define W2_FLUSH w2_flush
+#else
+#define W2_FLUSH v4_flush
+#endif
+
 #if defined(W2_NO_HELD_CONSTANTS) && !defined(W2_SCALARS_LOADED)
 #define W2_SCALARS_LOADED // (the scalars' vector copies sit beside W2Held)
 #endif
@@ -1071,7 +1127,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_
             const uint32_t D4 = ((uint32_t) Pm.eff_dim + 3u) & ~3u, nb1 = D4 / 4u;
             int *const lds_list = reinterpret_cast<int *>(&lds_x[L.list_off]);
             __builtin_amdgcn_s_setprio(2);
-            if (qn + 64u > wave_uniform(L.qcap)) { SECTION_PARAMS(Pf); v4_flush(Pf, L, qn, lane); }
+            if (qn + 64u > wave_uniform(L.qcap)) { SECTION_PARAMS(Pf); W2_FLUSH(Pf, L, qn, lane); }
             // ---- decide (parked chain lanes), as k_mutate_v4: slot A = the current state when it is left, else y; slot B = y when
             // z is adopted, else z
             int commit = 0, kind = 0; // kind: 0 nothing / finished, 1 next mutation, 2 second stage
@@ -1251,9 +1307,9 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_
     // the epilogue of k_mutate_v4, on its own copy of the block
     SECTION_PARAMS(Pe);
     const V4Layout<RULE_ORBITAL> Y = v4_layout<RULE_ORBITAL>(Pe, V4_QCAP);
-    if (qn + 32u > Y.L.qcap) v4_flush(Pe, Y.L, qn, lane);
+    if (qn + 32u > Y.L.qcap) W2_FLUSH(Pe, Y.L, qn, lane);
     v4_enqueue(Y.L, qn, live && cum > 0.f, cs.cur.px, cs.cur.py, cs.cur.r * cum, cs.cur.g * cum, cs.cur.b * cum);
-    v4_flush(Pe, Y.L, qn, lane);
+    W2_FLUSH(Pe, Y.L, qn, lane);
     if (live) {
         RowSampler smp = Y.smp;
         smp.set_roles(roles, Y.group, sub);
@@ -1268,6 +1324,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_
     if (lane == 0) atomicAdd(Pe.stats + 9, decided);
 }
 #undef W2_SECTION
+#undef W2_FLUSH
 
 // ------------------------------------------------------------------------------------------
 // k_mutate_v5: the chain loop with MORE RAYS THAN LANES (all three types).

@@ -1,0 +1,78 @@
+"""k_mutate_w2's film flush (kernels.hip: w2_film_put_channel, w2_flush_passes, w2_flush) issues its no-return atomics and never
+waits for them: a test of the BUILD, not of the GPU. kernels.hip is compiled to assembly once, with the unit's flags from the
+Makefile plus -S --cuda-device-only -gline-tables-only (about two minutes of CPU), and the instructions of k_mutate_w2 that the
+flush's source lines produced -- theirs, and those of everything they inline -- are read with tools/isa_waits.py:
+
+  inside the pass loops (w2_film_put_channel, w2_flush_passes): no s_waitcnt names vmcnt, no vector-memory load;
+  outside them (w2_flush): per flush site exactly one vector-memory load, the staging of the filter table, with one wait.
+
+The atomics are counted too: the test would pass vacuously on a section without any. The line ranges are read from the source."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+import bsdf_probe
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "drmlt-mitsuba_amd", "csrc")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import isa_waits  # noqa: E402
+
+FLUSH_SITES = 3  # the bookkeeping branch's and the epilogue's two
+
+
+def routine_lines(src, head):
+    """first and last line (1-based) of the routine whose definition starts with `head` at the beginning of a line"""
+    first = next(i for i, l in enumerate(src) if l.startswith(head))
+    last = next(i for i in range(first, len(src)) if src[i] == "}")
+    return first + 1, last + 1
+
+
+@pytest.fixture(scope="module")
+def flush_asm(tmp_path_factory):
+    hipcc = bsdf_probe._make_var("HIPCC")[0]
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("no hipcc")
+    out = str(tmp_path_factory.mktemp("w2_flush_isa") / "kernels.s")
+    r = subprocess.run([hipcc, "--offload-arch=" + bsdf_probe._make_var("ARCH")[0], *bsdf_probe.flags("kernels"), "-S", "--cuda-device-only",
+                        "-gline-tables-only", "-o", out, "kernels.hip"], cwd=CSRC, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    src = open(os.path.join(CSRC, "kernels.hip")).read().split("\n")
+    put = routine_lines(src, "template <bool BOX> DEV void w2_film_put_channel(")
+    passes = routine_lines(src, "template <bool BOX> DEV void w2_flush_passes(")
+    flush = routine_lines(src, "DEV void w2_flush(")
+    assert put[1] < passes[0] and passes[1] < flush[0], "the pass loops' routines stand together, in front of w2_flush"
+    sites = [i + 1 for i, l in enumerate(src) if re.search(r"\bW2_FLUSH\(", l)]
+    assert len(sites) == FLUSH_SITES, sites
+    ranges = {"passes": (put[0], passes[1]), "staging": flush}
+    print("source lines:", ranges, "flush sites:", sites)
+    return isa_waits.scan(open(out).read(), "k_mutate_w2", "kernels.hip", ranges), sites
+
+
+def test_no_wait_for_the_atomics_inside_the_pass_loops(flush_asm):
+    res, _ = flush_asm
+    c = res["passes"]
+    print(dict((k, v) for k, v in c.items() if k != "where"), c["where"])
+    # the box nest and the tabulated nest of every site, one atomic each (the three channels are three lanes)
+    assert c["vmem_atomic"] == 2 * FLUSH_SITES
+    assert c["lds"] > 0, "the queue rows and the staged table are read from LDS"
+    assert c["wait_vmcnt"] == 0, c["where"]
+    assert c["vmem_load"] == 0, c["where"]
+
+
+def test_one_staging_load_and_its_wait_outside_them(flush_asm):
+    res, sites = flush_asm
+    c = res["staging"]
+    print(dict((k, v) for k, v in c.items() if k != "where"), c["where"])
+    assert c["vmem_atomic"] == 0
+    for site in sites:
+        mine = [t for _, s, t in c["where"] if s == site]
+        loads = [t for t in mine if t.startswith(("flat_load", "global_load"))]
+        waits = [t for t in mine if t.startswith("s_waitcnt")]
+        assert len(loads) == 1 and len(waits) == 1, (site, mine)
+        assert mine.index(loads[0]) < mine.index(waits[0]), (site, mine)
+    assert c["vmem_load"] == FLUSH_SITES and c["wait_vmcnt"] == FLUSH_SITES, c["where"]

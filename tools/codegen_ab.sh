@@ -4,9 +4,10 @@
 # (drmlt-mitsuba_amd/variants/ is git-ignored; DRMLT_LIBRARY makes the binding load another build of the same ABI).
 # k_mutate_w2's ingredient switches (kernels.hip) are source switches, built the same way through CXXFLAGS, e.g.
 #   make -B OUT=../variants/libH.so CXXFLAGS="<the Makefile's CXXFLAGS> -DW2_NO_HELD_CONSTANTS"   (likewise -DW2_SCALARS_LOADED, -DW2_TWO_PHILOX,
-#   -DW2_MASKED_STEP, -DW2_COPIED_HANDOFF, -DW2_MASKED_TRACE)
+#   -DW2_MASKED_STEP, -DW2_COPIED_HANDOFF, -DW2_MASKED_TRACE, -DW2_SHARED_FLUSH: the film flush through v4_flush, as the twin)
 # and run with VARIANTS="A H ..." here or in codegen_ab_bench.sh (config 2). Nothing else builds them: after an edit to k_mutate_w2,
-# build all six once (no spill in any) and run tests/test_gpu_w2.py and tests/test_gpu_w2_step.py under DRMLT_LIBRARY.
+# build all seven once (no spill in any) and run tests/test_gpu_w2.py, tests/test_gpu_w2_step.py and
+# tests/test_gpu_w2_flush.py under DRMLT_LIBRARY.
 # Round 2: -amdgpu-early-ifcvt, -amdgpu-sched-strategy=max-ilp and raised SimplifyCFG phi-folding thresholds all stay within
 # +-1 % of the default build on config 2, config 3 and the soup.
 for v in ${VARIANTS:-A B D E}; do

@@ -3,7 +3,10 @@
 starts -- the last `file:line` of the .loc comment -- so a routine of a header counts where the kernel calls it. isa_region.py and
 isa_profile.py count by the innermost line instead: what a header routine costs, whoever calls it.
   python tools/isa_sections.py /tmp/k.s <mangled kernel> kernels.hip bookkeeping=1049-1190 rays=1191-1198 step=1199-1240
-Instructions of the kernel outside every section (and those without a line) are reported as `other`."""
+Instructions of the kernel outside every section (and those without a line) are reported as `other`.
+Per section it also reports `wait_vmcnt`, the s_waitcnt instructions that name vmcnt (loads, and on gfx9 no-return atomics and
+stores, count there: such a wait parks the wave until they have completed), and `vmem_load`, the vector-memory loads
+(flat_load*, global_load*)."""
 import collections
 import re
 import sys
@@ -36,6 +39,10 @@ for l in lines[st:en]:
     for w in WATCH:
         if w in op:
             kinds[sec][w] += 1
+    if op == 's_waitcnt' and 'vmcnt' in t:
+        kinds[sec]['wait_vmcnt'] += 1
+    if op.startswith(('flat_load', 'global_load')):
+        kinds[sec]['vmem_load'] += 1
 print('total', sum(count.values()))
 for name in [n for n, _, _ in sections] + ['other']:
     print('%-12s %5d  %s' % (name, count[name], dict(kinds[name])))
