@@ -604,6 +604,42 @@ template <bool TRI> DEV Hit trace_flat(const DParams &P, f3 o, f3 d, float tmin,
     return h;
 }
 
+// trace_flat with the scene's records held by the caller, in vector registers across its loop (k_mutate_w2h, kernels.hip): up to
+// three cuboids and one flat record, tested in the streaming loops' order by the same routines on the same values, then the same
+// tail (a copy: as a shared routine it would have to leave every kernel that inlines trace_flat register for register as it is).
+// No memory is read. Slots beyond the scene's counts are skipped by wave-uniform tests.
+struct HeldScene {
+    BoxRec box[3];
+    FlatRec flat;
+};
+DEV Hit trace_held(const HeldScene &S, uint32_t n_box, uint32_t n_flat, f3 o, f3 d, float tmin, float tmax) {
+    float best_t = tmax;
+    float2v best_uv = {0.f, 0.f};
+    int best_ks = -1;
+    if (n_box > 0u) test_box(S.box[0], o, d, tmin, best_t, best_uv, best_ks);
+    if (n_box > 1u) test_box(S.box[1], o, d, tmin, best_t, best_uv, best_ks);
+    if (n_box > 2u) test_box(S.box[2], o, d, tmin, best_t, best_uv, best_ks);
+    if (n_flat > 0u) test_flat<false>(S.flat, o, d, tmin, best_t, best_uv, best_ks);
+    Hit h{-1, best_t, best_uv.x, best_uv.y};
+    if (best_ks >= 0) {
+        if (best_ks & BOX_FACE_FLAG) { // a cuboid's face: its own (u, v) from the in-face coordinates, its own record
+            const uint32_t hc = (uint32_t) best_ks & 0xffffu;
+            const float uu = (hc & 2u) ? h.v : h.u, vv = (hc & 2u) ? h.u : h.v;
+            h.u = (hc & 4u) ? 1.f - uu : uu;
+            h.v = (hc & 8u) ? 1.f - vv : vv;
+            best_ks = (int) (((hc >> 4) & 3u) | ((hc >> 6) << 8));
+        }
+        h.prim = best_ks >> 8;
+        if ((best_ks & 0xff) == PRIM_QUAD2) { // sub-triangle (a,b,c) for v <= u, (a,c,d) otherwise; its own barycentrics
+            const bool second = h.v > h.u;
+            const float uu = second ? h.u : h.u - h.v, vv = second ? h.v - h.u : h.v;
+            h.prim += second ? 1 : 0;
+            h.u = uu; h.v = vv;
+        }
+    }
+    return h;
+}
+
 template <int FEAT = 15> DEV Hit trace(const DParams &P, f3 o, f3 d, float tmin, float tmax, bool any_hit) {
     if ((FEAT & 8) && P.use_bvh) return trace_bvh(P, o, d, tmin, tmax, any_hit);
     if (P.prims_flat) {

@@ -724,7 +724,8 @@ int drmlt_stats_get(drmlt_ctx *ctx, drmlt_stats *o) {
         fprintf(stderr, "[drmlt v4] waves through the orbital rule body: %llu\n", v[14]),
         fprintf(stderr, "[drmlt v4] waves through a one-light build: %llu\n", v[15]);
     if (ctx->knobs.verbose && ctx->P.kernel_variant == 4 && !(ctx->P.debug & 128)) // (slot 16 is a cycle stamp of the stamps builds)
-        fprintf(stderr, "[drmlt v4] waves through k_mutate_w2: %llu\n", v[16]);
+        fprintf(stderr, "[drmlt v4] waves through k_mutate_w2: %llu\n", v[16]),
+        fprintf(stderr, "[drmlt v4] waves with the ray records held in registers: %llu\n", v[17]); // (k_mutate_w2h; they count in slot 16 too)
     if ((ctx->P.debug & 1024) && v[20] && ctx->P.kernel_variant != 5)
         fprintf(stderr, "[drmlt bvh] lanes at slice start, of 64: tracing %.1f, chain waiting for its partner %.1f, chain parked for bookkeeping %.1f, helper idle %.1f, flush %.1f (%llu slices)\n",
                 (double) v[21] / v[20], (double) v[22] / v[20], (double) v[23] / v[20], (double) v[24] / v[20], (double) v[25] / v[20], v[20]);

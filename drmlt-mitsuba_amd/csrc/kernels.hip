@@ -1327,6 +1327,302 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_
 #undef W2_FLUSH
 
 // ------------------------------------------------------------------------------------------
+// k_mutate_w2h: k_mutate_w2 with the RAY PASS OVER RECORDS HELD IN VECTOR REGISTERS. A scene of one to three cuboids and at most
+// one flat record without plain triangles (bench.py's Cornell box: three cuboids and the light) has 58 dwords of records, which never
+// change during a launch. k_mutate_w2 streams them through two software-pipelined scalar loops in every iteration: the block's
+// pointers, then the records, counters, read-ahead and waits. Here they are read once, in the prologue, pinned like W2Held, and the
+// pass is straight-line code that reads no memory at all (device_path.h: trace_held -- test_box and test_flat as they are, in the
+// loops' order, on the same values: the same chains bit for bit). launch_mutate runs it where the plan says so (launch_plan.h:
+// w2_held_launch; DRMLT_NO_W2_HELD keeps k_mutate_w2). The loop is k_mutate_w2's in its default form, statement for statement;
+// a copy, not a template over both, because tests/test_w2_flush_isa.py pins k_mutate_w2's flush by the kernel's own call sites.
+// The flush sites call w2_flush by name. stats[14..16] as k_mutate_w2, and stats[17] counts the waves that ran this kernel.
+struct W2HeldScene {
+    HeldScene S;
+    uint32_t counts; // n_box | n_flat_rec << 8
+};
+// the twelve floats of a record's rows, pinned one by one, then as the vector pairs the tests read
+template <class Rec> DEV void w2_hold_rows(Rec &G, const float *c, const float *rz, bool have) {
+    float v[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) v[k] = 0.f;
+    if (have) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = c[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[8 + k] = rz[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) hold_v(v[k]);
+    G.cx = float2v{v[0], v[1]}; G.cy = float2v{v[2], v[3]}; G.cz = float2v{v[4], v[5]}; G.cw = float2v{v[6], v[7]};
+    G.z0 = v[8]; G.z1 = v[9]; G.z2 = v[10]; G.z3 = v[11];
+}
+// (a slot beyond the scene's count keeps zeros and is never tested; nothing past record n_box - 1 / n_flat_rec - 1 is read)
+DEV W2HeldScene w2_held_scene(const DParams &P) {
+    W2HeldScene H;
+    const uint32_t n_box = (uint32_t) min(max(P.n_box, 0), 3), n_flat = (uint32_t) min(max(P.n_flat_rec, 0), 1);
+#pragma unroll
+    for (uint32_t i = 0; i < 3u; ++i) {
+        BoxRec &G = H.S.box[i];
+        const DPrimBox *q = P.prims_box + i;
+        w2_hold_rows(G, q->c, q->rz, i < n_box);
+        uint32_t f0 = 0u, f1 = 0u, f2 = 0u;
+        if (i < n_box) { f0 = q->fw[0]; f1 = q->fw[1]; f2 = q->fw[2]; }
+        hold_v(f0); hold_v(f1); hold_v(f2);
+        G.f0 = f0; G.f1 = f1; G.f2 = f2;
+    }
+    FlatRec &F = H.S.flat;
+    w2_hold_rows(F, P.prims_flat->c, P.prims_flat->rz, n_flat > 0u);
+    int ks = -1;
+    if (n_flat > 0u) ks = P.prims_flat->kind_shade;
+    hold_v(ks);
+    F.ks = ks;
+    H.counts = n_box | (n_flat << 8);
+    hold_v(H.counts);
+    return H;
+}
+
+__global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32_t n_mut, uint32_t mut_base) {
+    typedef RowSamplerT<RULE_ORBITAL> RowSampler;
+    if (threadIdx.x == 0) { atomicAdd(P.stats + 14, 1ull); atomicAdd(P.stats + 15, 1ull); atomicAdd(P.stats + 16, 1ull); atomicAdd(P.stats + 17, 1ull); }
+    const uint32_t lane = threadIdx.x;
+    const uint32_t sub = lane & 31u;
+    const bool helper = lane >= 32u;
+    const uint32_t c = blockIdx.x * 32u + sub;
+    const bool live = !helper && c < P.n_chains;
+    const uint32_t cc = c < P.n_chains ? c : P.n_chains - 1;
+    const uint32_t S = V4_STRIDE;
+    int smp_mode = SM_STAGE1;
+    uint32_t roles;
+    uint32_t qn = 0u;
+    ChainState cs;
+    float cum = 0.f;
+    Counters ct = {0u, 0u, 0u, 0u, 0u};
+    PathState ps;
+    bool helper_has_ray = false;
+    Hit h{-1, 0.f, 0.f, 0.f};
+    int batch;
+    uint32_t base = 0u, target = 0u, limit = 0u;
+    bool reported = false;
+    W2Held held = w2_held(P);
+    w2_hold(held);
+    const W2HeldScene scene = w2_held_scene(P);
+    // (W2Held's companions: what the bookkeeping branch needs in SCALAR registers, one v_readfirstlane each where it opens)
+    uint32_t imp_lo = (uint32_t) (uintptr_t) P.importance, imp_hi = (uint32_t) ((uintptr_t) P.importance >> 32);
+    uint32_t done_lo = (uint32_t) (uintptr_t) P.chain_done, done_hi = (uint32_t) ((uintptr_t) P.chain_done >> 32);
+    uint32_t left_lo = (uint32_t) (uintptr_t) P.waves_left, left_hi = (uint32_t) ((uintptr_t) P.waves_left >> 32);
+    uint32_t key0_v = P.key0, key1_v = P.key1, chain_off_v = P.chain_offset, timid_v = (uint32_t) P.timid_after_large;
+    hold_v(imp_lo); hold_v(imp_hi); hold_v(done_lo); hold_v(done_hi); hold_v(left_lo); hold_v(left_hi);
+    hold_v(key0_v); hold_v(key1_v); hold_v(chain_off_v); hold_v(timid_v);
+    { // the prologue of k_mutate_v4
+        const V4Layout<RULE_ORBITAL> Y = v4_layout<RULE_ORBITAL>(P, V4_QCAP);
+        roles = RowSampler::first_roles(Y.group, sub);
+        if (!helper) {
+            for (uint32_t k = 0; k < Y.D; ++k) lds_x[k * S + sub] = unwrap01(P.x[(size_t) k * P.n_chains + cc]);
+            for (uint32_t k = Y.D; k < Y.D4; ++k) lds_x[k * S + sub] = 0.f;
+        }
+        cs.cur.lum = P.cur_lum[cc]; cs.cur.px = P.cur_px[cc]; cs.cur.py = P.cur_py[cc];
+        cs.cur.r = P.cur_r[cc]; cs.cur.g = P.cur_g[cc]; cs.cur.b = P.cur_b[cc];
+        cs.y = cs.cur; cs.z = cs.cur;
+        cs.a1 = 0.f; cs.coin_acc1 = cs.coin_acc2 = cs.coin_mix = 0.f;
+        cs.it = 0u; cs.nd1 = cs.nd2 = 0u; cs.stage = -1; cs.large = false;
+        path_init(P, ps);
+        base = (P.chain_done && live) ? P.chain_done[cc] : mut_base;
+        target = P.chain_done ? n_mut : mut_base + n_mut;
+        limit = P.chain_done ? P.run_limit : target;
+        ps.phase = (live && base < limit) ? PH_DONE : PH_IDLE;
+        ps.o = mk3(0.f, 0.f, 0.f); ps.d = mk3(0.f, 0.f, 1.f); ps.tmin = 0.f; ps.tmax = 0.f;
+        batch = P.mh_batch > 32 ? 32 : P.mh_batch;
+        stage_tables(P, Y.LT, lane);
+        if (!helper) {
+            const u4 coins = philox4x32_10(P.key0, P.key1, 0u, base, P.chain_offset + blockIdx.x * 32u + sub, TAG_COIN);
+            float *dst = &lds_x[Y.L.coin_off + sub];
+            dst[0] = u32_to_unit(coins.x); dst[S] = u32_to_unit(coins.y); dst[2u * S] = u32_to_unit(coins.z); dst[3u * S] = u32_to_unit(coins.w);
+        }
+    }
+
+    for (;;) {
+        const bool parked = ps.phase == PH_DONE;
+        const unsigned long long pmask = __ballot(parked);
+        const unsigned long long rmask = __ballot(ps.phase != PH_DONE && ps.phase != PH_IDLE);
+        if (!pmask && !rmask) break;
+        if (pmask && (__popcll(pmask) >= batch || !rmask)) {
+            // the branch's scalars, as k_mutate_w2
+            DParams Pm{};
+            Pm.importance = uniform_ptr<const float>(imp_lo, imp_hi); Pm.width = (int) wave_uniform((uint32_t) held.width); Pm.height = (int) wave_uniform((uint32_t) held.height);
+            Pm.chain_done = uniform_ptr<uint32_t>(done_lo, done_hi); Pm.waves_left = uniform_ptr<uint32_t>(left_lo, left_hi);
+            Pm.key0 = wave_uniform(key0_v); Pm.key1 = wave_uniform(key1_v); Pm.chain_offset = wave_uniform(chain_off_v);
+            Pm.eff_dim = (int) wave_uniform((uint32_t) held.eff_dim); Pm.timid_after_large = (int) wave_uniform(timid_v);
+            Pm.use_mixture = 0; Pm.acceptance_map = 0; Pm.type = 2; // (the orbital rule: mh_decide<RULE_ORBITAL> reads none of them)
+            const W2Held &C = held;
+            const V4Lds L{C.coin_off, C.list_off, C.q_off, C.qcap};
+            RowSampler smp = w2_sampler(Pm.key0, Pm.key1);
+            smp.set_roles(roles, C.group, sub); smp.mode = smp_mode;
+            const uint32_t D4 = ((uint32_t) Pm.eff_dim + 3u) & ~3u, nb1 = D4 / 4u;
+            int *const lds_list = reinterpret_cast<int *>(&lds_x[L.list_off]);
+            __builtin_amdgcn_s_setprio(2);
+            if (qn + 64u > wave_uniform(L.qcap)) { SECTION_PARAMS(Pf); w2_flush(Pf, L, qn, lane); }
+            // ---- decide (parked chain lanes)
+            int commit = 0, kind = 0; // kind: 0 nothing / finished, 1 next mutation, 2 second stage
+            bool wantA = false, wantB = false;
+            float eAx = 0.f, eAy = 0.f, eAr = 0.f, eAg = 0.f, eAb = 0.f;
+            float eBx = 0.f, eBy = 0.f, eBr = 0.f, eBg = 0.f, eBb = 0.f;
+            if (parked) {
+                const MhDigest o = mh_decide<RULE_ORBITAL>(Pm, cs, smp, ps, ct);
+                if (o.decided) {
+                    cum += o.w.w0;
+                    const bool a1st = o.acc1, a2nd = o.acc2, adopt = a1st || a2nd;
+                    const DSplat sb = select_splat(a2nd, cs.y, cs.z);
+                    const float wb = a2nd ? o.w.w1 : o.w.w2;
+                    wantB = !a1st && wb > 0.f;
+                    eBx = sb.px; eBy = sb.py; eBr = sb.r * wb; eBg = sb.g * wb; eBb = sb.b * wb;
+                    const DSplat sa = select_splat(adopt, cs.cur, cs.y);
+                    const float wa = adopt ? cum : o.w.w1;
+                    wantA = wa > 0.f;
+                    eAx = sa.px; eAy = sa.py; eAr = sa.r * wa; eAg = sa.g * wa; eAb = sa.b * wa;
+                    if (adopt) {
+                        cum = a1st ? o.w.w1 : o.w.w2;
+                        cs.cur = select_splat(a1st, cs.y, cs.z);
+                    }
+                    commit = mh_commit_mode(o);
+                }
+                kind = cs.stage < 0 ? 4 : 2; // 4: between mutations -- resolved below
+            }
+            kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
+            v4_enqueue(L, qn, wantA, eAx, eAy, eAr, eAg, eAb);
+            v4_enqueue(L, qn, wantB, eBx, eBy, eBr, eBg, eBb);
+
+            // ---- commit: the chosen proposal's row group becomes the chain's x group
+            smp.adopt(commit);
+            roles = smp.roles();
+
+            // ---- start (parked chain lanes): the coins of the mutation that begins were drawn with the previous one
+            if (parked && kind == 1) {
+                const float *cn = &lds_x[L.coin_off + sub];
+                cs.large = cn[0] < C.p_large;
+                cs.coin_acc1 = cn[S]; cs.coin_acc2 = cn[2u * S]; cs.coin_mix = cn[3u * S];
+                cs.stage = 0;
+                cs.nd1 = cs.nd2 = 0u;
+            }
+
+            // ---- proposals of the chains that start a mutation, flattened; block nb1 = the four coins of the NEXT mutation
+            RowSampler smg = w2_sampler(Pm.key0, Pm.key1);
+            const uint32_t chain_base_g = Pm.chain_offset + blockIdx.x * 32u;
+            const uint32_t maj_mine = base + cs.it;
+            const unsigned info = roles | (cs.large ? 1u : 0u);
+            const uint32_t f1mask = (uint32_t) __ballot(kind == 1);
+            if (f1mask) {
+                if (kind == 1) lds_list[__builtin_amdgcn_mbcnt_lo(f1mask, 0u)] = (int) sub;
+                const uint32_t n = (uint32_t) __popc(f1mask), total = n * (nb1 + 1u);
+                const float rcp_n = 1.f / (float) n;
+                for (uint32_t fb = 0u; fb < total; fb += 64u) {
+                    const uint32_t i = fb + lane;
+                    const bool valid = i < total;
+                    const uint32_t ii = valid ? i : 0u;
+                    const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
+                    const uint32_t cj = (uint32_t) lds_list[j];
+                    const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
+                    const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
+                    smg.set_roles(inf, C.group, cj);
+                    const bool coin = b >= nb1;
+                    if (valid) {
+                        const u4 r = philox4x32_10(Pm.key0, Pm.key1, coin ? 0u : b, coin ? mj + 1u : mj, chain_base_g + cj, coin ? TAG_COIN : TAG_S1);
+                        const Unit4 u{{u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)}};
+                        if (!coin) row_fill_first_drawn(smg, b, u, (inf & 1u) != 0u);
+                        else {
+                            float *dst = &lds_x[L.coin_off + cj];
+                            dst[0] = u.v[0]; dst[S] = u.v[1]; dst[2u * S] = u.v[2]; dst[3u * S] = u.v[3];
+                        }
+                    }
+                }
+            }
+            const uint32_t f2mask = (uint32_t) __ballot(kind == 2);
+            if (f2mask) { // second-stage proposals (rare: rejected bold steps)
+                if (kind == 2) lds_list[__builtin_amdgcn_mbcnt_lo(f2mask, 0u)] = (int) sub;
+                const uint32_t nb2 = Pm.timid_after_large ? D4 / 4u : (D4 / 2u + 3u) / 4u;
+                const uint32_t n = (uint32_t) __popc(f2mask), total = n * nb2;
+                const float rcp_n = 1.f / (float) n;
+                for (uint32_t fb = 0u; fb < total; fb += 64u) {
+                    const uint32_t i = fb + lane;
+                    const bool valid = i < total;
+                    const uint32_t ii = valid ? i : 0u;
+                    const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
+                    const uint32_t cj = (uint32_t) lds_list[j];
+                    const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
+                    const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
+                    smg.set_roles(inf, C.group, cj);
+                    if (valid) smg.fill_second(b, D4, mj, chain_base_g + cj, (inf & 1u) != 0u);
+                }
+            }
+
+            // ---- begin the evaluation (parked chain lanes): film position and camera ray from the first two components
+            if (parked) {
+                if (kind == 0) ps.phase = PH_IDLE;
+                else {
+                    DParams Vb{}; // what path_init and path_begin read of the block
+                    Vb.exclude_direct = C.exclude_direct; Vb.width = C.width; Vb.height = C.height;
+                    Vb.tan_half_fov = C.tan_half_fov; Vb.inv_aspect = C.inv_aspect; Vb.near_clip = C.near_clip; Vb.far_clip = C.far_clip;
+#pragma unroll
+                    for (int q = 0; q < 12; ++q) Vb.cam[q] = C.cam[q];
+                    smp_mode = smp.mode = cs.stage == 0 ? SM_STAGE1 : SM_STAGE2;
+                    path_init(Vb, ps);
+                    const float v0 = smp.next(0u), v1 = smp.next(1u);
+                    path_begin(Vb, ps, v0, v1);
+                }
+            }
+        }
+        // one ray per lane: chain lanes their camera / bounce ray, helpers the shadow ray they were handed. When any lane has a ray
+        // the whole wave runs the pass, whatever its lanes hold: registers in, registers out, and only lanes that traced read `h`
+        // (a PH_FLUSH step reads hit.prim, a held record's index or -1, and selects everything else away).
+        const bool tracing = helper ? helper_has_ray : ps.phase == PH_CLOSEST;
+        __builtin_amdgcn_s_setprio(0);
+        if (__ballot(tracing)) {
+            const uint32_t counts = wave_uniform(scene.counts);
+            h = trace_held(scene.S, counts & 0xffu, counts >> 8, ps.o, ps.d, ps.tmin, ps.tmax);
+        }
+        __builtin_amdgcn_s_setprio(3);
+        const unsigned occluded = from_upper_u((helper_has_ray && h.prim >= 0) ? 1u : 0u);
+        helper_has_ray = false;
+        ShadowRay sr;
+        asm volatile("" : "=v"(sr.d.x), "=v"(sr.d.y), "=v"(sr.d.z), "=v"(sr.tmin), "=v"(sr.tmax)); // whatever the registers hold: read under sr.valid only
+        sr.o = ps.o; sr.valid = false;
+        {
+            const W2Held &Cs = held;
+            if (!helper && ps.phase != PH_DONE && ps.phase != PH_IDLE) {
+                RowSampler sms = w2_sampler(0u, 0u);
+                sms.set_roles(roles, Cs.group, sub); sms.mode = smp_mode;
+                DParams Vs{}; // what path_step_diffuse reads of the block
+                Vs.eff_dim = Cs.eff_dim; Vs.rr_depth = Cs.rr_depth; Vs.max_depth = Cs.max_depth;
+                const LdsTables LT{Cs.shade_off, Cs.bsdf_off, 0u}; // (the emitter table is not read: HeldLightTables)
+                path_step_diffuse<RowSampler, HeldLightTables, false>(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
+            }
+        }
+        // hand the shadow ray of this vertex to the helper lane
+        ps.o.x = lower_keeps(ps.o.x, sr.o.x); ps.o.y = lower_keeps(ps.o.y, sr.o.y); ps.o.z = lower_keeps(ps.o.z, sr.o.z);
+        ps.d.x = lower_keeps(ps.d.x, sr.d.x); ps.d.y = lower_keeps(ps.d.y, sr.d.y); ps.d.z = lower_keeps(ps.d.z, sr.d.z);
+        ps.tmin = lower_keeps(ps.tmin, sr.tmin); ps.tmax = lower_keeps(ps.tmax, sr.tmax);
+        helper_has_ray = lower_keeps_u(0u, sr.valid ? 1u : 0u) != 0u; // (a chain lane keeps the `false` set above)
+    }
+    // the epilogue of k_mutate_v4, on its own copy of the block
+    SECTION_PARAMS(Pe);
+    const V4Layout<RULE_ORBITAL> Y = v4_layout<RULE_ORBITAL>(Pe, V4_QCAP);
+    if (qn + 32u > Y.L.qcap) w2_flush(Pe, Y.L, qn, lane);
+    v4_enqueue(Y.L, qn, live && cum > 0.f, cs.cur.px, cs.cur.py, cs.cur.r * cum, cs.cur.g * cum, cs.cur.b * cum);
+    w2_flush(Pe, Y.L, qn, lane);
+    if (live) {
+        RowSampler smp = Y.smp;
+        smp.set_roles(roles, Y.group, sub);
+        for (uint32_t k = 0; k < Y.D; ++k) Pe.x[(size_t) k * Pe.n_chains + c] = smp.x(k);
+        Pe.cur_lum[c] = cs.cur.lum; Pe.cur_px[c] = cs.cur.px; Pe.cur_py[c] = cs.cur.py;
+        Pe.cur_r[c] = cs.cur.r; Pe.cur_g[c] = cs.cur.g; Pe.cur_b[c] = cs.cur.b;
+        if (Pe.chain_done) Pe.chain_done[c] = base + cs.it;
+    }
+    if (Pe.chain_done && !reported && lane == 0) atomicSub(Pe.waves_left, 1u);
+    flush_counters(Pe, ct, lane);
+    const unsigned long long decided = wave_sum((live && !helper) ? cs.it : 0u);
+    if (lane == 0) atomicAdd(Pe.stats + 9, decided);
+}
+
+// ------------------------------------------------------------------------------------------
 // k_mutate_v5: the chain loop with MORE RAYS THAN LANES (all three types).
 //
 // In k_mutate_v4 a ray belongs to a lane: chain lane i traverses its camera / bounce ray, helper lane 32 + i the shadow ray
@@ -1959,6 +2255,7 @@ void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint
     // one-light twin when the scene has one light)
     case Build::V4_F0_STAMPS: LAUNCH_LIGHT(true, true);
     case Build::V4_F0: // (k_mutate_w2: the orbital one-light twin for launches without a third wave per SIMD -- plan.w2, launch_plan.h)
+        if (plan.w2_held && orbital && one_light) { LAUNCH(k_mutate_w2h); } // (its ray records in registers: plan.w2_held)
         if (plan.w2 && orbital && one_light) { LAUNCH(k_mutate_w2); }
         LAUNCH_LIGHT(true, false);
     case Build::V4_F3_STAMPS: LAUNCH(k_mutate_v4<3, true, true>); case Build::V4_F3: LAUNCH_RULE(3, true, false); case Build::V4_F7: LAUNCH_RULE(7, true, false);

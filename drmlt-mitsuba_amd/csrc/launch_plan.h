@@ -50,6 +50,7 @@ struct Knobs {
     bool no_run_ahead = false;               // DRMLT_NO_RUN_AHEAD
     bool rule_generic = false;               // DRMLT_RULE_GENERIC: k_mutate_v4 runs its generic body whatever the rule (device_types.h: rule_is_orbital)
     bool no_w2 = false;                      // DRMLT_NO_W2: the orbital one-light launches of V4_F0 stay on k_mutate_v4's twin (kernels.hip: k_mutate_w2)
+    bool no_w2_held = false;                 // DRMLT_NO_W2_HELD: k_mutate_w2 keeps streaming its ray records where k_mutate_w2h would hold them in registers (w2_held_launch below)
     bool one_light_generic = false;          // DRMLT_ONE_LIGHT_GENERIC: k_mutate_v4 reads the light from the staged tables however many the scene has (device_types.h: scene_has_one_light)
     long long ahead_cap = -1;               // DRMLT_AHEAD_CAP: mutations a chain may run beyond the launch's target; -1 = min(8 slices, 8192)
     bool mmlt_no_sort = false, no_regroup = false, regroup_on_host = false, regroup_check = false; // DRMLT_MMLT_NO_SORT, _NO_REGROUP, _REGROUP_ON_HOST, _REGROUP_CHECK
@@ -62,7 +63,7 @@ inline Knobs read_knobs() {
         {"DRMLT_VERBOSE", &K.verbose}, {"DRMLT_BVH_STACK32", &K.bvh_stack32}, {"DRMLT_NO_QUAD_MERGE", &K.no_quad_merge}, {"DRMLT_NO_BOX_MERGE", &K.no_box_merge},
         {"DRMLT_NO_FLAT_LOOP", &K.no_flat_loop}, {"DRMLT_FEAT_ALL", &K.feat_all}, {"DRMLT_NO_SMALL_TABLES", &K.no_small_tables},
         {"DRMLT_MMLT_TABLES_GLOBAL", &K.mmlt_tables_global}, {"DRMLT_BDPT_TABLES_GLOBAL", &K.bdpt_tables_global}, {"DRMLT_NO_RUN_AHEAD", &K.no_run_ahead},
-        {"DRMLT_RULE_GENERIC", &K.rule_generic}, {"DRMLT_ONE_LIGHT_GENERIC", &K.one_light_generic}, {"DRMLT_NO_W2", &K.no_w2},
+        {"DRMLT_RULE_GENERIC", &K.rule_generic}, {"DRMLT_ONE_LIGHT_GENERIC", &K.one_light_generic}, {"DRMLT_NO_W2", &K.no_w2}, {"DRMLT_NO_W2_HELD", &K.no_w2_held},
         {"DRMLT_MMLT_NO_SORT", &K.mmlt_no_sort}, {"DRMLT_NO_REGROUP", &K.no_regroup}, {"DRMLT_REGROUP_ON_HOST", &K.regroup_on_host}, {"DRMLT_REGROUP_CHECK", &K.regroup_check}};
     for (const auto &f : flags) *f.on = getenv(f.name) != nullptr;
     int v = 0;
@@ -98,6 +99,8 @@ struct PlanInputs {
     uint64_t scene_bytes = 0;                     // 4-wide nodes + intersection records (BVH scenes)
     int eff_dim = 0, max_depth = 0, mmlt_S = 0, mmlt_E = 0;
     int cus = 256;                                // compute units of the device
+    int n_box = 0, n_flat_rec = 0;                // records of the brute-force ray loop: cuboids, flat records that are no cuboid's face (flat scenes)
+    bool has_plain_tri = false;                   // any PRIM_TRIANGLE record among the flat ones
 };
 
 // one enumerator per chain-kernel instantiation that is launched (the launchers' switch statements name the template arguments)
@@ -124,6 +127,7 @@ struct ChainPlan {
     bool rows_mem = false;                   // k_mutate_v5's proposal rows in device memory (three waves per SIMD)
     int mh_batch = 0, trace_yield = 0, pool_refill = 0, trace_vote = 0;
     bool w2 = false;                         // V4_F0 only: launch_mutate may run k_mutate_w2 in place of the orbital one-light twin (w2_launch below)
+    bool w2_held = false;                    // ... and then k_mutate_w2h in place of k_mutate_w2: the scene's ray records fit its registers (w2_held_launch below)
     bool run_ahead = false;                  // drmlt_run: chains run beyond a launch's target towards the call's total
     bool verbose = false;
     std::string note;                        // the DRMLT_VERBOSE line of the path kernels' launches
@@ -145,6 +149,10 @@ inline bool path_mh(const PlanInputs &in) { return in.technique == DRMLT_TECH_PA
 // of the device. The ONE place the condition is written down.
 constexpr size_t CU_LDS_BYTES = 160u * 1024u;
 inline bool w2_launch(size_t lds, uint32_t grid, int cus) { return lds * 12u > CU_LDS_BYTES || (uint64_t) grid <= (uint64_t) cus * 4u * 2u; }
+// k_mutate_w2h (kernels.hip) is k_mutate_w2 with the scene's ray records held in vector registers: room for three cuboids and one
+// flat record, tested without the plain-triangle arm. A scene without cuboids gains nothing from it (cornell_c1: three flat
+// records) and keeps streaming. The ONE place the condition is written down.
+inline bool w2_held_launch(int n_box, int n_flat_rec, bool has_plain_tri) { return n_box >= 1 && n_box <= 3 && n_flat_rec >= 0 && n_flat_rec <= 1 && !has_plain_tri; }
 
 struct Family { int variant; bool tables_in_lds, rows_mem; };
 inline Family family(const PlanInputs &in, uint32_t n_chains, const Knobs &K) {
@@ -270,6 +278,7 @@ inline ChainPlan plan_chains(const PlanInputs &in, uint32_t n_chains, const Knob
             p.build = (F & 8) == 0 ? Build::V4_F7_GLOBAL : !s16 ? (F == 8 ? Build::V4_F8_S32_GLOBAL : Build::V4_F15_S32_GLOBAL) : ovf ? Build::V4_F15_OVF_GLOBAL
                     : stamps ? Build::V4_F15_STAMPS_GLOBAL : F == 8 ? Build::V4_F8_GLOBAL : Build::V4_F15_GLOBAL;
         p.w2 = p.build == Build::V4_F0 && !K.no_w2 && w2_launch(p.lds, p.grid, in.cus);
+        p.w2_held = p.w2 && !K.no_w2_held && w2_held_launch(in.n_box, in.n_flat_rec, in.has_plain_tri);
     } else { // k_mutate_v3, the cross-check: 32 chains per wave, rows of 32 floats; 0 = diffuse polygons, 3 = + rough conductor /
              // dielectric, 7 = + spheres, 15 = everything (BVH traversal); large scenes (tables in device memory): one general variant
         waves(32);

@@ -568,5 +568,6 @@ inline std::string prepare_scene(const drmlt_config &cfg, const drmlt_scene &sce
     in.n_shade = (uint32_t) P.n_shade; in.n_bsdfs = (uint32_t) P.n_bsdfs; in.n_emitters = (uint32_t) P.n_emitters;
     in.scene_bytes = P.use_bvh ? (uint64_t) P.n_bvh_nodes * sizeof(DBvh4Node) + out.prims.size() * sizeof(DPrim) : 0;
     in.eff_dim = P.eff_dim; in.max_depth = cfg.max_depth; in.mmlt_S = P.mmlt_S; in.mmlt_E = P.mmlt_E;
+    in.n_box = P.n_box; in.n_flat_rec = P.n_flat_rec; in.has_plain_tri = P.has_plain_tri != 0;
     return "";
 }

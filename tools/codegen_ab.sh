@@ -8,6 +8,8 @@
 # and run with VARIANTS="A H ..." here or in codegen_ab_bench.sh (config 2). Nothing else builds them: after an edit to k_mutate_w2,
 # build all seven once (no spill in any) and run tests/test_gpu_w2.py, tests/test_gpu_w2_step.py and
 # tests/test_gpu_w2_flush.py under DRMLT_LIBRARY.
+# k_mutate_w2h (the ray records held in registers) against k_mutate_w2 needs no second build: DRMLT_NO_W2_HELD=1 is a run-time
+# knob of the same library (launch_plan.h). The -DW2_* switches above are k_mutate_w2's alone; k_mutate_w2h has its default form.
 # Round 2: -amdgpu-early-ifcvt, -amdgpu-sched-strategy=max-ilp and raised SimplifyCFG phi-folding thresholds all stay within
 # +-1 % of the default build on config 2, config 3 and the soup.
 for v in ${VARIANTS:-A B D E}; do
