@@ -1276,7 +1276,13 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
 // orbital rule), the hand-off passes sr on, and nothing else looks at `ps`. A PH_FLUSH step (the path ended with its last shadow
 // ray pending) runs this routine once more: it reads ps.Li, ps.nee, ps.shadow_pending of what was written, all three as the masked
 // form leaves them, and selects everything else away (live = false).
-template <class SamplerT, class TablesT, bool MASKED = true>
+// RARE_EMITTER_HIT = true (k_mutate_w2h): the emitter-hit MIS block, two divisions among its instructions, runs only in an iteration in
+// which some stepping lane of the wave could use its result -- its bounce ray hit an emitter: live && hb && S.emitter >= 0 &&
+// ps.direct_on && ps.non_specular, a wave-uniform test like test_box's `hole` (in a Cornell box a percent or two of the rays, and
+// about 25 lanes step). When the block runs it is the block below, on every lane, with dn < 0 selecting as before; when it does
+// not, Li is what it was and dn, dr, lumPdf and Lm, which nothing else reads, are never computed -- not even as garbage.
+// -DW2H_EMITTER_HIT_ALWAYS restores the unconditional block in k_mutate_w2h.
+template <class SamplerT, class TablesT, bool MASKED = true, bool RARE_EMITTER_HIT = false>
 DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, SamplerT &smp, const Hit &hit, bool shadow_clear,
                            ShadowRay &sr) {
     static_assert(draws_batched<SamplerT>::value, "the five draws are requested together");
@@ -1297,7 +1303,7 @@ DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, Sa
     const f3 thr_b = hb ? ps.thr * ps.bweight : ps.thr;
     const float eta = hb ? ps.eta * ps.beta_eta : ps.eta;
     // emitter hit by the BSDF-sampled ray: MIS against direct sampling (refN is never zeroed without dielectrics)
-    {
+    if (!RARE_EMITTER_HIT || __ballot(live && hb && S.emitter >= 0 && ps.direct_on && ps.non_specular) != 0ull) {
         const DEmitter E = T.emitter(S.emitter >= 0 ? S.emitter : 0);
         const float dn = dot3(ps.d, n);
         const float dr = dot3(ps.d, ps.n);
@@ -1306,6 +1312,12 @@ DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, Sa
         lumPdf = (!ps.bdelta && dr >= 0.f) ? lumPdf : 0.f;
         const float a = ps.bpdf * ps.bpdf, b = lumPdf * lumPdf;
         const f3 Lm = fma3(thr_b * ld3(E.radiance), a / (a + b), Li);
+        if constexpr (RARE_EMITTER_HIT) {
+            // (the `if` below, behind the wave's test, is compiled to two nested exec-masked regions with the arithmetic above sunk
+            // into them; as a select on a condition without short cuts the block stays the straight-line block it is without the test)
+            const bool use = (live & hb & (S.emitter >= 0) & ps.direct_on & ps.non_specular) & (dn < 0.f);
+            Li = mk3(use ? Lm.x : Li.x, use ? Lm.y : Li.y, use ? Lm.z : Li.z);
+        } else
         if (live && hb && S.emitter >= 0 && ps.direct_on && ps.non_specular && dn < 0.f) Li = Lm;
     }
     const bool want_rr = hb && ps.depth >= P.rr_depth;

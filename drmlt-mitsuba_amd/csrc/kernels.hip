@@ -187,6 +187,92 @@ template <int RULE = RULE_GENERIC, class SamplerT> DEV MhDigest mh_decide(const 
     return d;
 }
 
+// k_mutate_w2h's decide: mh_decide<RULE_ORBITAL> and the caller's digest of its outcome (cumulative weight, the two queued splats,
+// adoption) WITHOUT ARMS. In the bookkeeping branch about 16 of 64 lanes are parked, and the arms of the state machine -- stage -1 /
+// 0 / 1, decided or not, adopted or not -- each sat behind a saved exec mask with a run of masked v_mov where they merge: the wave
+// paid every arm on every call. Here every lane of the branch, parked or not, computes the first-stage test, the orbital second-stage
+// test, the weights, the counter increments and both splats on whatever its registers hold, and selects choose what is kept: by
+// `parked`, by cs.stage and by the outcomes. A lane that is not parked, or parked with nothing evaluated (stage < 0: the first
+// call of a launch), keeps every value it had: no counter, weight or cs.it moves, and its splats are not wanted. The operations
+// that produce a kept value, and their order, are those of mh_decide / mh_digest / mh_first / mh_second_orbital / mh_weights /
+// mh_count and of the digest written out in k_mutate_w2: the same chains bit for bit (tests/test_gpu_w2h_decide.py).
+//   * the luminance test lum_invalid(res.lum) serves both stages (mh_first tests y's luminance, mh_digest z's: at either stage it
+//     is the evaluation just finished);
+//   * w1 = a1, w2 = (1 - a1) * a2, w0 = 1 - w1 - w2, then w2 = 0 without a second stage: at stage 0, a2 is 0 and 0 <= a1 <= 1, so
+//     w2 is +0 before it is cleared and w0 is 1 - a1 either way -- one expression serves both stages, in mh_weights' order;
+//   * what stays behind a branch is wave-uniform: the importance-map arm of the normalisation (P.importance; inside it, only lanes
+//     with an evaluation read the map -- another lane's pixel is stale or not yet set).
+// -DW2H_BRANCHED_DECIDE restores the call of mh_decide in k_mutate_w2h.
+struct W2hQueued { bool want; float px, py, r, g, b; };
+DEV void w2h_decide(const DParams &P, bool parked, ChainState &cs, const PathState &ps, Counters &ct, float &cum, int &commit, int &kind,
+                    W2hQueued &A, W2hQueued &B) {
+    const int stage = cs.stage;
+    const bool evald = parked && stage >= 0, first = evald && stage == 0, second = evald && stage != 0;
+    DSplat res;
+    res.px = ps.px; res.py = ps.py; res.r = ps.Li.x; res.g = ps.Li.y; res.b = ps.Li.z;
+    res.lum = luminance3(ps.Li);
+    if (P.importance) { // normalize_splat's first half
+        float lum = 0.f;
+        if (evald && !(res.r == 0.f && res.g == 0.f && res.b == 0.f)) {
+            const int ix = min(max(0, (int) res.px), P.width - 1), iy = min(max(0, (int) res.py), P.height - 1);
+            const float lv = P.importance[ix + iy * P.width];
+            res.r /= lv; res.g /= lv; res.b /= lv;
+            lum = luminance3(mk3(res.r, res.g, res.b));
+        }
+        res.lum = lum;
+    }
+    { // ... and its second
+        const float inv = 1.f / res.lum;
+        const bool pos = res.lum > 0.f;
+        res.r = pos ? res.r * inv : res.r; res.g = pos ? res.g * inv : res.g; res.b = pos ? res.b * inv : res.b;
+    }
+    ct.rays += evald ? ps.nrays : 0u;
+    const bool invalid = lum_invalid(res.lum), large = cs.large;
+    // first stage (mh_first, no mixture)
+    const float a1f = invalid ? 0.f : fminf(1.f, res.lum / cs.cur.lum);
+    const bool acc1f = a1f > 0.f && mh_flip(a1f, cs.coin_acc1);
+    const bool go_on = first && !acc1f && (P.timid_after_large != 0 || !large); // not decided: the second stage follows
+    // orbital second stage (mh_second_orbital on y's luminance, kept since stage 0)
+    const float y_lum = cs.y.lum, cur_lum = cs.cur.lum;
+    const bool reject = invalid || res.lum < y_lum, full = res.lum >= cur_lum;
+    const float ratio = (res.lum - y_lum) / (cur_lum - y_lum);
+    const float a2 = (!second || reject) ? 0.f : (full ? 1.f : ratio);
+    const bool acc2 = second && !reject && (full || mh_flip(ratio, cs.coin_acc2));
+    const bool acc1 = first && acc1f; // (an accepted first stage never goes on)
+    const bool decided = evald && !go_on;
+    cs.y = select_splat(first, res, cs.y);
+    cs.z = select_splat(second, res, cs.z);
+    const float a1 = first ? a1f : cs.a1;
+    cs.a1 = a1;
+    MhWeights w;
+    w.w1 = a1; w.w2 = (1.f - a1) * a2; w.w0 = 1.f - w.w1 - w.w2;
+    w.w2 = second ? w.w2 : 0.f;
+    { // mh_count, its increments under `decided`
+        const bool lg = decided && large, bold = decided && !large;
+        ct.large_acc1l += (lg ? 1u : 0u) + ((lg && acc1) ? 1u << 16 : 0u);
+        ct.acc1b_secl += ((bold && acc1) ? 1u : 0u) + ((lg && second) ? 1u << 16 : 0u);
+        ct.secb_acc2l += ((bold && second) ? 1u : 0u) + ((lg && acc2) ? 1u << 16 : 0u);
+        ct.acc2b_rev += (bold && acc2) ? 1u : 0u;
+    }
+    cs.it += decided ? 1u : 0u;
+    cs.stage = decided ? -1 : (go_on ? 1 : stage);
+    // the digest of k_mutate_w2: the current state collects its weight, a replaced state and the proposals are queued
+    cum = decided ? cum + w.w0 : cum;
+    const bool adopt = acc1 || acc2;
+    const float wb = acc2 ? w.w1 : w.w2;
+    B.want = decided && !acc1 && wb > 0.f;
+    B.px = acc2 ? cs.y.px : cs.z.px; B.py = acc2 ? cs.y.py : cs.z.py;
+    B.r = (acc2 ? cs.y.r : cs.z.r) * wb; B.g = (acc2 ? cs.y.g : cs.z.g) * wb; B.b = (acc2 ? cs.y.b : cs.z.b) * wb;
+    const float wa = adopt ? cum : w.w1;
+    A.want = decided && wa > 0.f;
+    A.px = adopt ? cs.cur.px : cs.y.px; A.py = adopt ? cs.cur.py : cs.y.py;
+    A.r = (adopt ? cs.cur.r : cs.y.r) * wa; A.g = (adopt ? cs.cur.g : cs.y.g) * wa; A.b = (adopt ? cs.cur.b : cs.y.b) * wa;
+    cum = adopt ? (acc1 ? w.w1 : w.w2) : cum;
+    cs.cur = select_splat(adopt, select_splat(acc1, cs.y, cs.z), cs.cur);
+    commit = acc1 ? SM_STAGE1 : (acc2 ? SM_STAGE2 : 0);
+    kind = parked ? (cs.stage < 0 ? 4 : 2) : 0; // 4: between mutations -- resolved by mh_resolve_kind
+}
+
 // k_mutate_v3: splat the decided mutation at once and adopt the accepted proposal. The three splats go through ONE
 // film_put site (the call expands to ~150 instructions; six inlined copies of it were a sixth of the kernel's code):
 // slot 0 current state, 1 first-stage, 2 second-stage proposal.
@@ -1333,8 +1419,10 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_
 // pointers, then the records, counters, read-ahead and waits. Here they are read once, in the prologue, pinned like W2Held, and the
 // pass is straight-line code that reads no memory at all (device_path.h: trace_held -- test_box and test_flat as they are, in the
 // loops' order, on the same values: the same chains bit for bit). launch_mutate runs it where the plan says so (launch_plan.h:
-// w2_held_launch; DRMLT_NO_W2_HELD keeps k_mutate_w2). The loop is k_mutate_w2's in its default form, statement for statement;
-// a copy, not a template over both, because tests/test_w2_flush_isa.py pins k_mutate_w2's flush by the kernel's own call sites.
+// w2_held_launch; DRMLT_NO_W2_HELD keeps k_mutate_w2). The loop is k_mutate_w2's in its default form, statement for statement,
+// but for two things of its own: the decide is w2h_decide, by selects (-DW2H_BRANCHED_DECIDE: k_mutate_w2's), and the step runs its
+// emitter-hit block only when a bounce ray of the wave hit the light (path_step_diffuse's RARE_EMITTER_HIT; -DW2H_EMITTER_HIT_ALWAYS).
+// A copy, not a template over both, because tests/test_w2_flush_isa.py pins k_mutate_w2's flush by the kernel's own call sites.
 // The flush sites call w2_flush by name. stats[14..16] as k_mutate_w2, and stats[17] counts the waves that ran this kernel.
 struct W2HeldScene {
     HeldScene S;
@@ -1461,8 +1549,15 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
             int *const lds_list = reinterpret_cast<int *>(&lds_x[L.list_off]);
             __builtin_amdgcn_s_setprio(2);
             if (qn + 64u > wave_uniform(L.qcap)) { SECTION_PARAMS(Pf); w2_flush(Pf, L, qn, lane); }
-            // ---- decide (parked chain lanes)
+            // ---- decide (parked chain lanes): by selects, no arm behind a divergent branch (w2h_decide)
             int commit = 0, kind = 0; // kind: 0 nothing / finished, 1 next mutation, 2 second stage
+#ifndef W2H_BRANCHED_DECIDE
+            W2hQueued qa, qb;
+            w2h_decide(Pm, parked, cs, ps, ct, cum, commit, kind, qa, qb);
+            kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
+            v4_enqueue(L, qn, qa.want, qa.px, qa.py, qa.r, qa.g, qa.b);
+            v4_enqueue(L, qn, qb.want, qb.px, qb.py, qb.r, qb.g, qb.b);
+#else
             bool wantA = false, wantB = false;
             float eAx = 0.f, eAy = 0.f, eAr = 0.f, eAg = 0.f, eAb = 0.f;
             float eBx = 0.f, eBy = 0.f, eBr = 0.f, eBg = 0.f, eBb = 0.f;
@@ -1490,6 +1585,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
             kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
             v4_enqueue(L, qn, wantA, eAx, eAy, eAr, eAg, eAb);
             v4_enqueue(L, qn, wantB, eBx, eBy, eBr, eBg, eBb);
+#endif
 
             // ---- commit: the chosen proposal's row group becomes the chain's x group
             smp.adopt(commit);
@@ -1593,7 +1689,12 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
                 DParams Vs{}; // what path_step_diffuse reads of the block
                 Vs.eff_dim = Cs.eff_dim; Vs.rr_depth = Cs.rr_depth; Vs.max_depth = Cs.max_depth;
                 const LdsTables LT{Cs.shade_off, Cs.bsdf_off, 0u}; // (the emitter table is not read: HeldLightTables)
-                path_step_diffuse<RowSampler, HeldLightTables, false>(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
+#ifndef W2H_EMITTER_HIT_ALWAYS
+                constexpr bool RARE_HIT = true; // the emitter-hit block only in an iteration in which a bounce ray hit the light
+#else
+                constexpr bool RARE_HIT = false;
+#endif
+                path_step_diffuse<RowSampler, HeldLightTables, false, RARE_HIT>(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
             }
         }
         // hand the shadow ray of this vertex to the helper lane

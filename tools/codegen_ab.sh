@@ -9,7 +9,9 @@
 # build all seven once (no spill in any) and run tests/test_gpu_w2.py, tests/test_gpu_w2_step.py and
 # tests/test_gpu_w2_flush.py under DRMLT_LIBRARY.
 # k_mutate_w2h (the ray records held in registers) against k_mutate_w2 needs no second build: DRMLT_NO_W2_HELD=1 is a run-time
-# knob of the same library (launch_plan.h). The -DW2_* switches above are k_mutate_w2's alone; k_mutate_w2h has its default form.
+# knob of the same library (launch_plan.h). The -DW2_* switches above are k_mutate_w2's alone; k_mutate_w2h has two of its own,
+# built the same way: -DW2H_BRANCHED_DECIDE (the decide through mh_decide and its arms, as k_mutate_w2) and -DW2H_EMITTER_HIT_ALWAYS
+# (the step's emitter-hit block in every iteration). The second spills four scalar registers: a build to be measured, not shipped.
 # Round 2: -amdgpu-early-ifcvt, -amdgpu-sched-strategy=max-ilp and raised SimplifyCFG phi-folding thresholds all stay within
 # +-1 % of the default build on config 2, config 3 and the soup.
 for v in ${VARIANTS:-A B D E}; do
