@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "drmlt_node_destroy", "drmlt_bootstrap_luminances", "drmlt_seed_indices", "drmlt_comm_info", "drmlt_film_tile",
     "drmlt_render_direct", "drmlt_direct_split", "drmlt_node_render_direct", "drmlt_render_bdpt",
     "drmlt_bdpt_layer_count", "drmlt_bdpt_layer_index", "drmlt_render_bdpt_layers",
+    "drmlt_seed_device", "drmlt_seed_pool_device", "drmlt_node_seed_device", "drmlt_select_seeds_device", "drmlt_select_seeds_blocked",
 )
 
 
@@ -113,6 +114,12 @@ def load_library():
     L.drmlt_render_direct.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p]
     L.drmlt_direct_split.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.drmlt_node_render_direct.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p]
+    L.drmlt_seed_device.argtypes = L.drmlt_seed.argtypes
+    L.drmlt_seed_pool_device.argtypes = L.drmlt_seed_pool.argtypes
+    L.drmlt_node_seed_device.argtypes = L.drmlt_node_seed.argtypes
+    L.drmlt_select_seeds_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.drmlt_select_seeds_blocked.argtypes = L.drmlt_select_seeds_device.argtypes[1:]
     _lib = L
     return L
 
@@ -169,6 +176,25 @@ class Context:
         b = C.c_double()
         self._chk(self.L.drmlt_seed_pool(self.h, seed, first_chain, pool_chains, C.byref(b)))
         return b.value
+
+    # -- the same with the selection on the device (drmlt_seed_device: no luminance readback)
+    def seed_device(self, seed, chain_offset=0):
+        b = C.c_double()
+        self._chk(self.L.drmlt_seed_device(self.h, seed, chain_offset, C.byref(b)))
+        return b.value
+
+    def seed_pool_device(self, seed, first_chain, pool_chains):
+        b = C.c_double()
+        self._chk(self.L.drmlt_seed_pool_device(self.h, seed, first_chain, pool_chains, C.byref(b)))
+        return b.value
+
+    def select_seeds_device(self, lum, seed, stream, n_select, weights=None):
+        """The selection alone, by the device's kernels, on caller-supplied samples: (sorted indices, mean, total weight)."""
+        lum, weights = _seed_arrays(lum, weights)
+        out, mean, total = np.zeros(n_select, dtype=np.uint32), C.c_double(), C.c_double()
+        self._chk(self.L.drmlt_select_seeds_device(self.h, lum.ctypes.data, None if weights is None else weights.ctypes.data, lum.size, seed, stream,
+                                                   n_select, out.ctypes.data, C.byref(mean), C.byref(total)))
+        return out, mean.value, total.value
 
     # -- film exchange over RCCL, called from C++ inside the library (one process per GPU)
     def comm_init(self, unique_id, rank, world):
@@ -337,6 +363,27 @@ class Context:
         return np.frombuffer(cur, dtype=SPLAT_DTYPE).copy(), u
 
 
+def _seed_arrays(lum, weights):
+    lum = np.ascontiguousarray(lum, dtype=np.float32)
+    if weights is not None:
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        assert weights.shape == lum.shape
+    return lum, weights
+
+
+def select_seeds_blocked(lum, seed, stream, n_select, weights=None):
+    """Context.select_seeds_device on the host, no device: csrc/seed_select.h run serially. The two agree bit for bit."""
+    L = load_library()
+    lum, weights = _seed_arrays(lum, weights)
+    out, mean, total = np.zeros(n_select, dtype=np.uint32), C.c_double(), C.c_double()
+    rc = L.drmlt_select_seeds_blocked(lum.ctypes.data, None if weights is None else weights.ctypes.data, lum.size, seed, stream, n_select,
+                                      out.ctypes.data, C.byref(mean), C.byref(total))
+    if rc != 0:
+        raise DrmltError(rc, "seed selection: the mean of the samples is zero, or no sample has a finite positive weight" if rc == abi.E_ZERO_LUM
+                         else "seed selection: invalid arguments")
+    return out, mean.value, total.value
+
+
 def luminance_map(rgb_small, width, height):
     """BidirectionalUtils::mltLuminancePass tail: first-stage image -> full-size luminance image."""
     L = load_library()
@@ -449,6 +496,11 @@ class Node:
     def seed(self, seed):
         b = C.c_double()
         self._chk(self.L.drmlt_node_seed(self.h, seed, C.byref(b)))
+        return b.value
+
+    def seed_device(self, seed):
+        b = C.c_double()
+        self._chk(self.L.drmlt_node_seed_device(self.h, seed, C.byref(b)))
         return b.value
 
     def run(self, total_mutations, stop=None, progress=None):

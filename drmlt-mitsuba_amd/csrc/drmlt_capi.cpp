@@ -6,6 +6,7 @@
 #include "drmlt_ctx.h"
 #include "scene_prep.h"
 #include "bdpt_layers.h"
+#include "seed_select.h"
 
 #include <hip/hip_runtime.h>
 
@@ -47,6 +48,10 @@ void launch_layers_bdpt(const DParams &P, uint32_t n, float scale, float *layers
 // the direct-illumination pass (kernels_direct.hip)
 uint32_t direct_grid(const DirectJob &J, int width);
 void launch_render_direct(const DParams &P, const DirectJob &J, float *out, hipStream_t st);
+// seed selection on the device (kernels_seed.hip)
+size_t seed_workspace_bytes(uint32_t n);
+hipError_t launch_seed_select(const float *lum, const float *wts, uint32_t n, uint32_t k0, uint32_t k1, uint32_t stream, uint32_t n_select, uint32_t slice_lo,
+                              uint32_t slice_n, void *work, uint32_t *out_index, float *out_lum, const double **sums_out, hipStream_t st);
 
 namespace {
 
@@ -256,7 +261,8 @@ int drmlt_set_stream(drmlt_ctx *ctx, void *hip_stream) {
 // `pool_chains` seeds are drawn for, the whole job (every rank repeats this cheap step and gets the same list and the
 // same b); this context then takes seeds [chain_offset, chain_offset + work_units) of the sorted list. A job split over
 // several contexts runs exactly the chains one context with pool_chains work units would.
-static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint32_t pool_chains, double *b_out) {
+// `on_device`: the middle -- mean, table, picks, their ordering -- runs in kernels_seed.hip instead of on one host core.
+static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint32_t pool_chains, double *b_out, bool on_device) {
     if (!ctx) return DRMLT_E_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DParams &P = ctx->P;
@@ -294,74 +300,105 @@ static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint3
     else if (bdpt) launch_bootstrap_bdpt(P, n, d_lum.as<float>(), ctx->plan.aux_lds, ctx->stream);
     else launch_bootstrap(P, n, d_lum.as<float>(), ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
-    std::vector<float> lum((size_t) n * (weighted_seeds ? 2 : 1));
-    HIP_TRY(ctx, hipMemcpyAsync(lum.data(), d_lum.p, lum.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    P.boot_weighted = 0;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-
-    // generateSeeds, pathsampler.cpp:879-954: mean over non-NaN samples, CDF over the non-zero ones
-    double sum = 0.0, tok = 0.0;
-    std::vector<uint32_t> idx;
-    std::vector<double> cdf;
-    idx.reserve(n);
-    cdf.reserve((size_t) n + 1); // (hundreds of millions of samples with technique=mmlt's derived chain count: no reallocation on the way)
-    cdf.push_back(0.0);
-    for (uint32_t i = 0; i < n; ++i) {
-        float l = lum[i];
-        if (std::isnan(l)) continue;
-        tok += 1.0;
-        sum += (double) l;
-        const float lw = weighted_seeds ? lum[(size_t) n + i] : l; // what the seed is drawn in proportion to
-        if (l != 0.f && lw > 0.f && std::isfinite(lw)) { idx.push_back(i); cdf.push_back(cdf.back() + (double) lw); }
-    }
-    double mean = tok > 0 ? sum / tok : 0.0;
-    if (mmlt) mean *= (double) ctx->cfg.max_depth; // "As we split the path by corresponding depth"
-    if (!(mean > 0.0))
-        return ctx->fail(DRMLT_E_ZERO_LUM, "The average image luminance appears to be zero! This could indicate a problem with the scene setup.");
-    if (idx.empty()) // mean(f) > 0, yet no sample can seed a chain: every contribution lies where the importance map is zero (or not finite)
-        return ctx->fail(DRMLT_E_ZERO_LUM, "No bootstrap sample has a finite positive luminance under the importance map (average luminance %g): "
-                                           "the map is zero wherever the scene contributes; firstStageSeeding=reference seeds from the plain luminance", mean);
-    const double norm = 1.0 / cdf.back();
-    for (size_t i = 1; i < cdf.size(); ++i) cdf[i] *= norm;
-    cdf.back() = 1.0;
-    // One pick per chain: DiscreteDistribution::sample on the uniform of its own stream address. The picks are SORTED afterwards
-    // (PathSeedSortPredicate), so the order in which they are made is free: the uniforms are sorted first and the table is walked once,
-    // each lower_bound galloping on from the previous one -- the same entry as a search of the whole table, without a million cold binary
-    // searches through gigabytes (technique=mmlt derives a million chains and 50 x maxDepth bootstrap samples for each).
-    std::vector<double> xis(n_select);
-    for (uint32_t j = 0; j < n_select; ++j) {
-        uint32_t r[4];
-        philox_host(P.key0, P.key1, 0u, j, P.boot_stream, TAG_SEEDSEL, r);
-        xis[j] = (double) ((float) (r[0] >> 8) * (1.0f / 16777216.0f));
-    }
-    std::sort(xis.begin(), xis.end());
-    std::vector<uint32_t> seed_index(n_select);
-    size_t from = 0; // lower_bound of the previous (smaller or equal) uniform: the next one's is not before it
-    for (uint32_t j = 0; j < n_select; ++j) {
-        const double xi = xis[j];
-        size_t step = 1, hi = from;
-        while (hi < cdf.size() && cdf[hi] < xi) { from = hi + 1; hi += step; step *= 2; }
-        auto entry = std::lower_bound(cdf.begin() + from, cdf.begin() + std::min(hi, cdf.size()), xi);
-        from = (size_t) (entry - cdf.begin());
-        size_t index = (size_t) std::max<ptrdiff_t>(0, (entry - cdf.begin()) - 1);
-        index = std::min(cdf.size() - 2, index);
-        while (cdf[index + 1] - cdf[index] == 0 && index < cdf.size() - 1) ++index;
-        seed_index[j] = idx[index];
-    }
-    std::sort(seed_index.begin(), seed_index.end()); // PathSeedSortPredicate
-    if (pool) { // this context's slice of the job's seed list
-        std::vector<uint32_t> mine(seed_index.begin() + chain_offset, seed_index.begin() + chain_offset + ctx->n_chains);
-        seed_index.swap(mine);
-    }
-    ctx->seed_indices = seed_index;
-    std::vector<float> seed_lum(ctx->n_chains);
-    for (uint32_t j = 0; j < ctx->n_chains; ++j) seed_lum[j] = lum[seed_index[j]];
-
+    double mean = 0.0;
+    std::vector<uint32_t> seed_index;
     DevBuf d_si, d_sl;
-    HIP_TRY(ctx, d_si.alloc(seed_index.size() * sizeof(uint32_t)));
-    HIP_TRY(ctx, d_sl.alloc(seed_lum.size() * sizeof(float)));
-    HIP_TRY(ctx, hipMemcpyAsync(d_si.p, seed_index.data(), seed_index.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(d_sl.p, seed_lum.data(), seed_lum.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (!on_device) {
+        std::vector<float> lum((size_t) n * (weighted_seeds ? 2 : 1));
+        HIP_TRY(ctx, hipMemcpyAsync(lum.data(), d_lum.p, lum.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        P.boot_weighted = 0;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+        // generateSeeds, pathsampler.cpp:879-954: mean over non-NaN samples, CDF over the non-zero ones
+        double sum = 0.0, tok = 0.0;
+        std::vector<uint32_t> idx;
+        std::vector<double> cdf;
+        idx.reserve(n);
+        cdf.reserve((size_t) n + 1); // (hundreds of millions of samples with technique=mmlt's derived chain count: no reallocation on the way)
+        cdf.push_back(0.0);
+        for (uint32_t i = 0; i < n; ++i) {
+            float l = lum[i];
+            if (std::isnan(l)) continue;
+            tok += 1.0;
+            sum += (double) l;
+            const float lw = weighted_seeds ? lum[(size_t) n + i] : l; // what the seed is drawn in proportion to
+            if (l != 0.f && lw > 0.f && std::isfinite(lw)) { idx.push_back(i); cdf.push_back(cdf.back() + (double) lw); }
+        }
+        mean = tok > 0 ? sum / tok : 0.0;
+        if (mmlt) mean *= (double) ctx->cfg.max_depth; // "As we split the path by corresponding depth"
+        if (!(mean > 0.0))
+            return ctx->fail(DRMLT_E_ZERO_LUM, "The average image luminance appears to be zero! This could indicate a problem with the scene setup.");
+        if (idx.empty()) // mean(f) > 0, yet no sample can seed a chain: every contribution lies where the importance map is zero (or not finite)
+            return ctx->fail(DRMLT_E_ZERO_LUM, "No bootstrap sample has a finite positive luminance under the importance map (average luminance %g): "
+                                               "the map is zero wherever the scene contributes; firstStageSeeding=reference seeds from the plain luminance", mean);
+        const double norm = 1.0 / cdf.back();
+        for (size_t i = 1; i < cdf.size(); ++i) cdf[i] *= norm;
+        cdf.back() = 1.0;
+        // One pick per chain: DiscreteDistribution::sample on the uniform of its own stream address. The picks are SORTED afterwards
+        // (PathSeedSortPredicate), so the order in which they are made is free: the uniforms are sorted first and the table is walked once,
+        // each lower_bound galloping on from the previous one -- the same entry as a search of the whole table, without a million cold binary
+        // searches through gigabytes (technique=mmlt derives a million chains and 50 x maxDepth bootstrap samples for each).
+        std::vector<double> xis(n_select);
+        for (uint32_t j = 0; j < n_select; ++j) {
+            uint32_t r[4];
+            philox_host(P.key0, P.key1, 0u, j, P.boot_stream, TAG_SEEDSEL, r);
+            xis[j] = (double) ((float) (r[0] >> 8) * (1.0f / 16777216.0f));
+        }
+        std::sort(xis.begin(), xis.end());
+        seed_index.assign(n_select, 0u);
+        size_t from = 0; // lower_bound of the previous (smaller or equal) uniform: the next one's is not before it
+        for (uint32_t j = 0; j < n_select; ++j) {
+            const double xi = xis[j];
+            size_t step = 1, hi = from;
+            while (hi < cdf.size() && cdf[hi] < xi) { from = hi + 1; hi += step; step *= 2; }
+            auto entry = std::lower_bound(cdf.begin() + from, cdf.begin() + std::min(hi, cdf.size()), xi);
+            from = (size_t) (entry - cdf.begin());
+            size_t index = (size_t) std::max<ptrdiff_t>(0, (entry - cdf.begin()) - 1);
+            index = std::min(cdf.size() - 2, index);
+            while (cdf[index + 1] - cdf[index] == 0 && index < cdf.size() - 1) ++index;
+            seed_index[j] = idx[index];
+        }
+        std::sort(seed_index.begin(), seed_index.end()); // PathSeedSortPredicate
+        if (pool) { // this context's slice of the job's seed list
+            std::vector<uint32_t> mine(seed_index.begin() + chain_offset, seed_index.begin() + chain_offset + ctx->n_chains);
+            seed_index.swap(mine);
+        }
+        ctx->seed_indices = seed_index;
+        std::vector<float> seed_lum(ctx->n_chains);
+        for (uint32_t j = 0; j < ctx->n_chains; ++j) seed_lum[j] = lum[seed_index[j]];
+
+        HIP_TRY(ctx, d_si.alloc(seed_index.size() * sizeof(uint32_t)));
+        HIP_TRY(ctx, d_sl.alloc(seed_lum.size() * sizeof(float)));
+        HIP_TRY(ctx, hipMemcpyAsync(d_si.p, seed_index.data(), seed_index.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(d_sl.p, seed_lum.data(), seed_lum.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        // The same selection on the device (kernels_seed.hip; the rule, its summation order and the pick are seed_select.h's, cited there
+        // against pathsampler.cpp:936-957): no luminance leaves the device, no host allocation grows with n. What comes back is three
+        // doubles and this context's n_chains picks, which the bookkeeping below and drmlt_seed_indices read.
+        P.boot_weighted = 0;
+        const size_t work_bytes = seed_workspace_bytes(n);
+        DevBuf d_work; // freed on every return path, and before the chains are initialised
+        if (d_work.alloc(work_bytes) != hipSuccess)
+            return ctx->fail(DRMLT_E_DEVICE, "seed selection on the device: allocation of %zu bytes of workspace failed (%u bootstrap samples)", work_bytes, n);
+        if (ctx->knobs.verbose) fprintf(stderr, "[drmlt] seed selection on the device: %zu bytes of workspace beside %zu bytes of luminances (%u samples, %u picks)\n", work_bytes, d_lum.bytes, n, n_select);
+        HIP_TRY(ctx, d_si.alloc((size_t) ctx->n_chains * sizeof(uint32_t)));
+        HIP_TRY(ctx, d_sl.alloc((size_t) ctx->n_chains * sizeof(float)));
+        const double *d_sums = nullptr;
+        HIP_TRY(ctx, launch_seed_select(d_lum.as<float>(), weighted_seeds ? d_lum.as<float>() + n : nullptr, n, P.key0, P.key1, P.boot_stream, n_select,
+                                        pool ? chain_offset : 0u, ctx->n_chains, d_work.p, d_si.as<uint32_t>(), d_sl.as<float>(), &d_sums, ctx->stream));
+        double sums[3] = {0.0, 0.0, 0.0}; // total weight, sum, tok
+        seed_index.assign(ctx->n_chains, 0u);
+        HIP_TRY(ctx, hipMemcpyAsync(sums, d_sums, sizeof sums, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(seed_index.data(), d_si.p, seed_index.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        const int status = seed_status(sums[1], sums[2], sums[0], mmlt ? (double) ctx->cfg.max_depth : 1.0, &mean);
+        if (status == SEED_SELECT_ZERO_MEAN)
+            return ctx->fail(DRMLT_E_ZERO_LUM, "The average image luminance appears to be zero! This could indicate a problem with the scene setup.");
+        if (status == SEED_SELECT_NO_WEIGHT)
+            return ctx->fail(DRMLT_E_ZERO_LUM, "No bootstrap sample has a finite positive luminance under the importance map (average luminance %g): "
+                                               "the map is zero wherever the scene contributes; firstStageSeeding=reference seeds from the plain luminance", mean);
+        ctx->seed_indices = seed_index;
+    }
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_err.p, 0, 64, ctx->stream));
     HIP_TRY(ctx, ensure_overflow(ctx, P, 2 * (size_t) P.n_chains_alloc));
     if (mmlt && !ctx->knobs.mmlt_no_sort) {
@@ -370,7 +407,10 @@ static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint3
         std::vector<uint32_t> order(padded, n);
         for (uint32_t j = 0; j < n; ++j) order[j] = j;
         const uint32_t md = (uint32_t) ctx->cfg.max_depth;
+        const auto t_sort = std::chrono::steady_clock::now();
         std::stable_sort(order.begin(), order.begin() + n, [&](uint32_t a, uint32_t b) { return seed_index[a] % md > seed_index[b] % md; });
+        if (ctx->knobs.verbose) // (this ordering stays on the host under both seed passes: its share of seed_ms)
+            fprintf(stderr, "[drmlt] seed: depth ordering of %u chains on the host, %.3f ms\n", n, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_sort).count());
         HIP_TRY(ctx, ctx->d_order.alloc(order.size() * sizeof(uint32_t)));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // `order` is a local
@@ -408,7 +448,8 @@ static int seed_impl(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, uint3
     return DRMLT_OK;
 }
 
-int drmlt_seed(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, double *b_out) { return seed_impl(ctx, seed, chain_offset, 0u, b_out); }
+int drmlt_seed(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, double *b_out) { return seed_impl(ctx, seed, chain_offset, 0u, b_out, false); }
+int drmlt_seed_device(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, double *b_out) { return seed_impl(ctx, seed, chain_offset, 0u, b_out, true); }
 
 int drmlt_bootstrap_luminances(drmlt_ctx *ctx, uint64_t seed, uint32_t stream, uint32_t n, float *out) {
     if (!ctx || !out) return DRMLT_E_INVALID;
@@ -439,7 +480,50 @@ int drmlt_seed_indices(drmlt_ctx *ctx, uint32_t *out) {
 int drmlt_seed_pool(drmlt_ctx *ctx, uint64_t seed, uint32_t first_chain, uint32_t pool_chains, double *b_out) {
     if (!ctx) return DRMLT_E_INVALID;
     if (pool_chains == 0) return ctx->fail(DRMLT_E_INVALID, "drmlt_seed_pool: pool_chains must be positive");
-    return seed_impl(ctx, seed, first_chain, pool_chains, b_out);
+    return seed_impl(ctx, seed, first_chain, pool_chains, b_out, false);
+}
+
+int drmlt_seed_pool_device(drmlt_ctx *ctx, uint64_t seed, uint32_t first_chain, uint32_t pool_chains, double *b_out) {
+    if (!ctx) return DRMLT_E_INVALID;
+    if (pool_chains == 0) return ctx->fail(DRMLT_E_INVALID, "drmlt_seed_pool_device: pool_chains must be positive");
+    return seed_impl(ctx, seed, first_chain, pool_chains, b_out, true);
+}
+
+// The selection alone on caller-supplied samples (test utilities, like drmlt_bootstrap_luminances): on the device ...
+int drmlt_select_seeds_device(drmlt_ctx *ctx, const float *lum, const float *weights_or_null, uint32_t n, uint64_t seed, uint32_t stream, uint32_t n_select,
+                              uint32_t *out_sorted, double *mean_out, double *total_out) {
+    if (!ctx || !lum || !out_sorted) return DRMLT_E_INVALID;
+    if (n == 0 || n > 0x7fffffffu || n_select == 0) return ctx->fail(DRMLT_E_INVALID, "drmlt_select_seeds_device: between 1 and 2^31 - 1 samples and at least one pick");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t work_bytes = seed_workspace_bytes(n);
+    DevBuf d_lum, d_work, d_out;
+    HIP_TRY(ctx, d_lum.alloc((size_t) n * (weights_or_null ? 2 : 1) * sizeof(float)));
+    HIP_TRY(ctx, d_out.alloc((size_t) n_select * sizeof(uint32_t)));
+    if (d_work.alloc(work_bytes) != hipSuccess)
+        return ctx->fail(DRMLT_E_DEVICE, "seed selection on the device: allocation of %zu bytes of workspace failed (%u samples)", work_bytes, n);
+    HIP_TRY(ctx, hipMemcpyAsync(d_lum.p, lum, (size_t) n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if (weights_or_null) HIP_TRY(ctx, hipMemcpyAsync(d_lum.as<float>() + n, weights_or_null, (size_t) n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    const double *d_sums = nullptr;
+    HIP_TRY(ctx, launch_seed_select(d_lum.as<float>(), weights_or_null ? d_lum.as<float>() + n : nullptr, n, (uint32_t) seed, (uint32_t) (seed >> 32), stream, n_select, 0u,
+                                    n_select, d_work.p, d_out.as<uint32_t>(), nullptr, &d_sums, ctx->stream));
+    double sums[3] = {0.0, 0.0, 0.0};
+    HIP_TRY(ctx, hipMemcpyAsync(sums, d_sums, sizeof sums, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out_sorted, d_out.p, (size_t) n_select * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    double mean = 0.0;
+    const int status = seed_status(sums[1], sums[2], sums[0], 1.0, &mean);
+    if (mean_out) *mean_out = mean;
+    if (total_out) *total_out = sums[0];
+    if (status != SEED_SELECT_OK) return ctx->fail(DRMLT_E_ZERO_LUM, status == SEED_SELECT_ZERO_MEAN ? "the mean of the samples is not positive" : "no sample has a finite positive weight");
+    return DRMLT_OK;
+}
+
+// ... and on the host, with no device: seed_select.h run serially
+int drmlt_select_seeds_blocked(const float *lum, const float *weights_or_null, uint32_t n, uint64_t seed, uint32_t stream, uint32_t n_select, uint32_t *out_sorted,
+                               double *mean_out, double *total_out) {
+    if (!lum || !out_sorted || n == 0 || n > 0x7fffffffu || n_select == 0) return DRMLT_E_INVALID;
+    const int status = seed_select_host(lum, weights_or_null, n, (uint32_t) seed, (uint32_t) (seed >> 32), stream, n_select, 1.0, out_sorted, mean_out, total_out);
+    return status == SEED_SELECT_OK ? DRMLT_OK : DRMLT_E_ZERO_LUM;
 }
 
 // Two-stage MLT (drmlt.cpp:406-418): the luminance image of the first stage weights the second stage's splats.

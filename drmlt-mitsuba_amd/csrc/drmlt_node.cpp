@@ -365,6 +365,19 @@ int drmlt_node_seed(drmlt_node *node, uint64_t seed, double *b_out) {
     return DRMLT_OK;
 }
 
+// ... with every rank's selection on its device (drmlt_seed_pool_device)
+int drmlt_node_seed_device(drmlt_node *node, uint64_t seed, double *b_out) {
+    if (!node) return DRMLT_E_INVALID;
+    const uint32_t n = node->subs[0]->n_chains, total = n * (uint32_t) node->subs.size();
+    std::vector<double> b(node->subs.size(), 0.0);
+    int rc = for_each_rank(node, [&](int r) { return drmlt_seed_pool_device(node->subs[r], seed, (uint32_t) r * n, total, &b[r]); });
+    if (rc != DRMLT_OK) return rc;
+    node->b = b[0];
+    node->seeded = true;
+    if (b_out) *b_out = node->b;
+    return DRMLT_OK;
+}
+
 // total_mutations over ALL chains of the node; the callback reports rank 0's progress scaled to the job
 int drmlt_node_run(drmlt_node *node, uint64_t total_mutations, volatile int *stop, drmlt_progress_cb cb, void *user) {
     if (!node) return DRMLT_E_INVALID;

@@ -159,9 +159,15 @@ public:
         m_cfg.sample_count = props.getInteger("sampleCount", 4); // the independent sampler's sampleCount (default 4)
         m_device = props.getInteger("device", 0);
         m_seed = (uint64_t) props.getInteger("seed", 0x5EED);
+        // where generateSeeds' selection runs: on one host core (drmlt_seed) or on the device (drmlt_seed_device), both stages alike
+        std::string seedPass = props.getString("seedPass", "host");
+        if (seedPass == "host") m_seedOnDevice = false;
+        else if (seedPass == "device") m_seedOnDevice = true;
+        else throw std::runtime_error("Unknown seedPass (host | device)");
     }
 
     const drmlt_config &config() const { return m_cfg; }
+    bool seedOnDevice() const { return m_seedOnDevice; }
     void cancel() { m_stop = 1; } // asynchronous, like Integrator::cancel (integrator.h:77-84)
 
     // DRMLT::render: seeding -> chain loop -> develop. `out` receives W*H*3 floats.
@@ -182,7 +188,7 @@ public:
             drmlt_ctx *first = drmlt_create(&c1, &small, m_device, err, sizeof err);
             if (!first) throw std::runtime_error(err);
             std::vector<float> img((size_t) small.camera.width * small.camera.height * 3);
-            int rc1 = drmlt_seed(first, m_seed, 0, nullptr);
+            int rc1 = m_seedOnDevice ? drmlt_seed_device(first, m_seed, 0, nullptr) : drmlt_seed(first, m_seed, 0, nullptr);
             if (rc1 == DRMLT_OK) rc1 = drmlt_run(first, (uint64_t) small.camera.width * small.camera.height * (uint64_t) c1.sample_count, &m_stop, nullptr, nullptr);
             if (rc1 == DRMLT_OK) rc1 = drmlt_develop(first, nullptr, img.data());
             std::string msg1 = rc1 == DRMLT_OK ? "" : drmlt_last_error(first);
@@ -196,7 +202,7 @@ public:
         if (!ctx) throw std::runtime_error(err);
         double b = 0;
         int rc = importance.empty() ? DRMLT_OK : drmlt_set_importance_map(ctx, importance.data());
-        if (rc == DRMLT_OK) rc = drmlt_seed(ctx, m_seed, 0, &b);
+        if (rc == DRMLT_OK) rc = m_seedOnDevice ? drmlt_seed_device(ctx, m_seed, 0, &b) : drmlt_seed(ctx, m_seed, 0, &b);
         if (rc == DRMLT_OK) {
             uint64_t total = (uint64_t) sc.camera.width * sc.camera.height * (uint64_t) m_cfg.sample_count;
             rc = drmlt_run(ctx, total, &m_stop, nullptr, nullptr);
@@ -226,7 +232,7 @@ public:
 private:
     drmlt_config m_cfg;
     int m_device = 0, m_firstStageSizeReduction = 16;
-    bool m_twoStage = false;
+    bool m_twoStage = false, m_seedOnDevice = false;
     uint64_t m_seed = 0x5EED;
     volatile int m_stop = 0;
 };

@@ -30,10 +30,10 @@ int main(int argc, char **argv) {
         const drmlt_config &c = integrator.config();
         if (check) {
             printf("technique=%d type=%d maxDepth=%d rrDepth=%d directSamples=%d luminanceSamples=%d pLarge=%g workUnits=%d "
-                   "sigma=%g scaleSecond=%g acceptanceMap=%d timidAfterLarge=%d useMixture=%d sampleCount=%d integrator=%s kelemenStyleMutation=%d kelemenStyleWeights=%d\n",
+                   "sigma=%g scaleSecond=%g acceptanceMap=%d timidAfterLarge=%d useMixture=%d sampleCount=%d integrator=%s kelemenStyleMutation=%d kelemenStyleWeights=%d seedPass=%s\n",
                    c.technique, c.type, c.max_depth, c.rr_depth, c.direct_samples, c.luminance_samples, c.p_large, c.work_units,
                    c.sigma, c.scale_second, c.acceptance_map, c.timid_after_large, c.use_mixture, c.sample_count,
-                   c.algo == DRMLT_ALGO_PSSMLT ? "pssmlt" : "drmlt", c.kelemen_style_mutation, c.kelemen_style_weights);
+                   c.algo == DRMLT_ALGO_PSSMLT ? "pssmlt" : "drmlt", c.kelemen_style_mutation, c.kelemen_style_weights, integrator.seedOnDevice() ? "device" : "host");
             return 0;
         }
         if (scene.empty()) throw std::runtime_error("no scene file given");

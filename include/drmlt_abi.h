@@ -449,6 +449,7 @@ typedef struct drmlt_node drmlt_node;
 drmlt_node *drmlt_node_create(const drmlt_config *cfg, const drmlt_scene *scene,
                               uint32_t device_mask, char *err, size_t errlen);
 int drmlt_node_seed(drmlt_node *node, uint64_t seed, double *b_out);
+int drmlt_node_seed_device(drmlt_node *node, uint64_t seed, double *b_out); /* every rank through drmlt_seed_pool_device (below) */
 int drmlt_node_run(drmlt_node *node, uint64_t total_mutations, volatile int *stop,
                    drmlt_progress_cb cb, void *user);
 int drmlt_node_develop(drmlt_node *node, const float *direct_rgb_or_null, float *out_rgb);
@@ -461,6 +462,34 @@ int drmlt_node_device_count(drmlt_node *node);
 drmlt_ctx *drmlt_node_context(drmlt_node *node, int rank); /* borrowed; for film / chain inspection */
 const char *drmlt_node_last_error(drmlt_node *node);
 void drmlt_node_destroy(drmlt_node *node);
+
+/* ---- seed selection on the device ------------------------------------------
+ * drmlt_seed, drmlt_seed_pool and drmlt_node_seed with the middle of
+ * generateSeeds -- the mean, the table, the picks (DiscreteDistribution::sample
+ * with the zero-width skip, pathsampler.cpp:936-957) and their ordering
+ * (PathSeedSortPredicate) -- run by kernels over the bootstrap luminances where
+ * the bootstrap kernel left them: no luminance is copied to the host, no host
+ * allocation grows with the sample count, only this context's picks come back
+ * (drmlt_seed_indices reads them as before). The sums are fp64 in a fixed
+ * blocked order (csrc/seed_select.h), so the result does not depend on how the
+ * kernels are scheduled; it equals the host calls' wherever a pick's uniform
+ * does not lie within rounding (samples * 2^-51) of a boundary of the table,
+ * and b agrees to that relative bound. State, errors, seed_ms: as the host calls. */
+int drmlt_seed_device(drmlt_ctx *ctx, uint64_t seed, uint32_t chain_offset, double *b_out);
+int drmlt_seed_pool_device(drmlt_ctx *ctx, uint64_t seed, uint32_t first_chain,
+                           uint32_t pool_chains, double *b_out);
+/* Test utilities, like drmlt_bootstrap_luminances: the selection alone (pathsampler.cpp:936-957) on caller-supplied samples.
+ * lum: n luminances; weights_or_null: what they are drawn in proportion to (the luminance under the importance map), or NULL
+ * for the luminances themselves. out_sorted: n_select sample indices, ascending. *mean_out: the mean over the non-NaN
+ * samples; *total_out: the total weight as summed (both may be NULL). DRMLT_E_ZERO_LUM when the mean or every weight is zero.
+ * _device runs the kernels on ctx's device; _blocked is the same header run serially on the host, no device needed: the two
+ * agree bit for bit. */
+int drmlt_select_seeds_device(drmlt_ctx *ctx, const float *lum, const float *weights_or_null, uint32_t n,
+                              uint64_t seed, uint32_t stream, uint32_t n_select, uint32_t *out_sorted,
+                              double *mean_out, double *total_out);
+int drmlt_select_seeds_blocked(const float *lum, const float *weights_or_null, uint32_t n,
+                               uint64_t seed, uint32_t stream, uint32_t n_select, uint32_t *out_sorted,
+                               double *mean_out, double *total_out);
 
 const char *drmlt_last_error(drmlt_ctx *ctx);
 uint32_t drmlt_abi_version(void);
