@@ -1281,7 +1281,7 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
 // ps.direct_on && ps.non_specular, a wave-uniform test like test_box's `hole` (in a Cornell box a percent or two of the rays, and
 // about 25 lanes step). When the block runs it is the block below, on every lane, with dn < 0 selecting as before; when it does
 // not, Li is what it was and dn, dr, lumPdf and Lm, which nothing else reads, are never computed -- not even as garbage.
-// -DW2H_EMITTER_HIT_ALWAYS restores the unconditional block in k_mutate_w2h.
+// (Commit b65b601 last carried a switch that compiled the unconditional block into k_mutate_w2h for an A/B run.)
 template <class SamplerT, class TablesT, bool MASKED = true, bool RARE_EMITTER_HIT = false>
 DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, SamplerT &smp, const Hit &hit, bool shadow_clear,
                            ShadowRay &sr) {

@@ -187,7 +187,7 @@ template <int RULE = RULE_GENERIC, class SamplerT> DEV MhDigest mh_decide(const 
     return d;
 }
 
-// k_mutate_w2h's decide: mh_decide<RULE_ORBITAL> and the caller's digest of its outcome (cumulative weight, the two queued splats,
+// k_mutate_w2<true>'s decide (w2h): mh_decide<RULE_ORBITAL> and the caller's digest of its outcome (cumulative weight, the two queued splats,
 // adoption) WITHOUT ARMS. In the bookkeeping branch about 16 of 64 lanes are parked, and the arms of the state machine -- stage -1 /
 // 0 / 1, decided or not, adopted or not -- each sat behind a saved exec mask with a run of masked v_mov where they merge: the wave
 // paid every arm on every call. Here every lane of the branch, parked or not, computes the first-stage test, the orbital second-stage
@@ -195,14 +195,14 @@ template <int RULE = RULE_GENERIC, class SamplerT> DEV MhDigest mh_decide(const 
 // `parked`, by cs.stage and by the outcomes. A lane that is not parked, or parked with nothing evaluated (stage < 0: the first
 // call of a launch), keeps every value it had: no counter, weight or cs.it moves, and its splats are not wanted. The operations
 // that produce a kept value, and their order, are those of mh_decide / mh_digest / mh_first / mh_second_orbital / mh_weights /
-// mh_count and of the digest written out in k_mutate_w2: the same chains bit for bit (tests/test_gpu_w2h_decide.py).
+// mh_count and of the digest written out in k_mutate_w2<false>: the same chains bit for bit (tests/test_gpu_w2h_decide.py).
 //   * the luminance test lum_invalid(res.lum) serves both stages (mh_first tests y's luminance, mh_digest z's: at either stage it
 //     is the evaluation just finished);
 //   * w1 = a1, w2 = (1 - a1) * a2, w0 = 1 - w1 - w2, then w2 = 0 without a second stage: at stage 0, a2 is 0 and 0 <= a1 <= 1, so
 //     w2 is +0 before it is cleared and w0 is 1 - a1 either way -- one expression serves both stages, in mh_weights' order;
 //   * what stays behind a branch is wave-uniform: the importance-map arm of the normalisation (P.importance; inside it, only lanes
 //     with an evaluation read the map -- another lane's pixel is stale or not yet set).
-// -DW2H_BRANCHED_DECIDE restores the call of mh_decide in k_mutate_w2h.
+// (Commit b65b601 last carried a switch that compiled the other form into this instantiation for an A/B run.)
 struct W2hQueued { bool want; float px, py, r, g, b; };
 DEV void w2h_decide(const DParams &P, bool parked, ChainState &cs, const PathState &ps, Counters &ct, float &cum, int &commit, int &kind,
                     W2hQueued &A, W2hQueued &B) {
@@ -256,7 +256,7 @@ DEV void w2h_decide(const DParams &P, bool parked, ChainState &cs, const PathSta
     }
     cs.it += decided ? 1u : 0u;
     cs.stage = decided ? -1 : (go_on ? 1 : stage);
-    // the digest of k_mutate_w2: the current state collects its weight, a replaced state and the proposals are queued
+    // the digest of k_mutate_w2<false>: the current state collects its weight, a replaced state and the proposals are queued
     cum = decided ? cum + w.w0 : cum;
     const bool adopt = acc1 || acc2;
     const float wb = acc2 ? w.w1 : w.w2;
@@ -728,9 +728,6 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(
             if (qn + 64u > L.qcap) { SECTION_PARAMS(Pf); v4_flush(Pf, L, qn, lane); } // room for this branch's splats (at most 2 per chain)
             // ---- decide (parked chain lanes): weights, commit mode, what the chain does next
             int commit = 0, kind = 0; // kind: 0 nothing / finished, 1 next mutation, 2 second stage, 3 Green's reverse
-            // A decided mutation queues at most two splats (mh_digest: an accepted first stage has no second, w2 = 0):
-            //   y adopted: {cur}    z adopted: {cur, y}    neither: {y, z}
-            // slot A = the current state when it is left, else y; slot B = y when z is adopted, else z
             bool wantA = false, wantB = false;
             float eAx = 0.f, eAy = 0.f, eAr = 0.f, eAg = 0.f, eAb = 0.f;
             float eBx = 0.f, eBy = 0.f, eBr = 0.f, eBg = 0.f, eBb = 0.f;
@@ -954,7 +951,6 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(
         for (int q = 0; q < 6; ++q) atomicAdd(Pe.stats + 26 + q, (unsigned long long) hist[q]);
         atomicAdd(Pe.stats + 22, t_decide); atomicAdd(Pe.stats + 23, t_commit); atomicAdd(Pe.stats + 24, t_start); atomicAdd(Pe.stats + 25, t_fill);
     }
-
     if (live) {
         RowSampler smp = Y.smp;
         smp.set_roles(roles, Y.group, sub);
@@ -976,44 +972,55 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(
 }
 
 // ------------------------------------------------------------------------------------------
-// k_mutate_w2: k_mutate_v4<V4_ONE_LIGHT_BUILD | V4_ORBITAL_BUILD, true, false> -- flat scene, tables in LDS, orbital rule, one area
-// light -- compiled for TWO waves per SIMD. launch_mutate runs it in place of that twin on launches that cannot have a third
+// k_mutate_w2<HELD>: k_mutate_v4<V4_ONE_LIGHT_BUILD | V4_ORBITAL_BUILD, true, false> -- flat scene, tables in LDS, orbital rule, one
+// area light -- compiled for TWO waves per SIMD. launch_mutate runs it in place of that twin on launches that cannot have a third
 // wave on a SIMD (launch_plan.h: w2_launch), bench.py's flagship line among them: there the twin's 168-register bound buys
 // nothing, and a wave's rate is its own serial time, instructions plus the waits one partner cannot cover. A kernel of its own
 // name because the v3 / v4 / v5 instantiations are pinned register by register (tests/test_kernel_resources_smooth.py).
 // Same chains bit for bit: the LDS layout, the run-ahead protocol, the splat queue, the prologue and epilogue are k_mutate_v4's,
-// every floating-point expression is a header routine it shares with the twin. What differs (DESIGN.md section 7a has the
-// measurements; each can be compiled out for an A/B run):
-//   -DW2_NO_HELD_CONSTANTS  off: the wave-uniform constants that are only ever VALU operands or LDS address terms -- layout offsets,
-//                           the light's two records, the camera, p_large, the roulette depths -- are read ONCE, in the prologue,
-//                           and stay in vector registers (W2Held); the step and the bookkeeping branch open without a scalar load
-//                           or v4_layout. The step's wait chain is otherwise the twin's: five component reads, a wait, the hit's
-//                           shading record, a wait, the BSDF record.
-//   -DW2_SCALARS_LOADED     off: what the bookkeeping branch needs in SCALAR registers (the importance map, chain_done, waves_left,
-//                           the Philox keys, chain_offset, eff_dim, timid_after_large) waits in vector registers too and comes
-//                           back with one v_readfirstlane each: thirteen VALU instructions for a scalar-cache round trip. The ray
-//                           pass reads its record pointers and counts as k_mutate_v4 does (holding them measured slower).
-//   -DW2_TWO_PHILOX         off: a fill item computes its counter and tag per lane and calls Philox ONCE; only the tail differs
-//                           (row_fill_first_drawn for a proposal block, four writes for a coin block).
-//   -DW2_MASKED_STEP        off: the step writes the vertex, the bounce, ps.nee and the shadow ray on every lane that steps and selects
-//                           only what a path that has ended is still read for (path_step_diffuse<.., MASKED = false>, device_path.h,
-//                           lists each field and where it is set anew); the twin's two masked copy-back blocks are gone.
-//   -DW2_COPIED_HANDOFF     off: the shadow ray reaches the helper lanes in ONE v_permlane32_swap per value (lower_keeps: a chain lane
-//                           keeps its own ray, its helper receives the shadow ray) in place of a broadcast from the lower half and
-//                           a block of masked moves on the helpers.
-//   -DW2_MASKED_TRACE       off: when any lane has a ray the WHOLE wave runs the ray pass (a wave-uniform test, no saved exec mask and
-//                           no masked merge of the hit), and the shadow ray of a lane that does not step is left undefined instead
-//                           of being set to zeros and copies. The ray loops read memory through scalar loads only, so a lane without
-//                           a ray computes garbage and touches nothing; `h` is read by lanes that traced, and by a PH_FLUSH step, which
-//                           uses hit.prim -- a record's index or -1 -- for an LDS address and selects everything else away.
-//   -DW2_SHARED_FLUSH       off: the film flush is w2_flush (below): the box filter and the tabulated filters in separate loop nests,
-//                           the table read from LDS, so that no wait inside a flush names vmcnt and the film's no-return atomics
-//                           are never waited for (+1.0 % with the box filter, -0.9 % with the Gaussian, where the atomics are
-//                           the bound). With the switch the three flush sites call v4_flush as the twin does.
+// every floating-point expression is a header routine it shares with the twin. What differs, ingredient by ingredient (DESIGN.md section 7a has the measurements; commit b65b601
+// last carried a source switch for each, which compiled the twin's form back in for an A/B run):
+//   held constants    the wave-uniform constants that are only ever VALU operands or LDS address terms -- layout offsets, the light's
+//                     two records, the camera, p_large, the roulette depths -- are read ONCE, in the prologue, and stay in vector
+//                     registers (W2Held); the step and the bookkeeping branch open without a scalar load or v4_layout. The step's wait
+//                     chain is otherwise the twin's: five component reads, a wait, the hit's shading record, a wait, the BSDF record.
+//   held scalars      what the bookkeeping branch needs in SCALAR registers (the importance map, chain_done, waves_left, the Philox
+//                     keys, chain_offset, eff_dim, timid_after_large) waits in vector registers too and comes back with one
+//                     v_readfirstlane each: thirteen VALU instructions for a scalar-cache round trip. The streaming ray pass reads
+//                     its record pointers and counts as k_mutate_v4 does (holding them measured slower).
+//   one Philox site   a fill item computes its counter and tag per lane and calls Philox ONCE; only the tail differs
+//                     (row_fill_first_drawn for a proposal block, four writes for a coin block).
+//   unmasked step     the step writes the vertex, the bounce, ps.nee and the shadow ray on every lane that steps and selects only what a
+//                     path that has ended is still read for (path_step_diffuse<.., MASKED = false>, device_path.h, lists each field
+//                     and where it is set anew); the twin's two masked copy-back blocks are gone.
+//   swapped hand-off  the shadow ray reaches the helper lanes in ONE v_permlane32_swap per value (lower_keeps: a chain lane keeps its
+//                     own ray, its helper receives the shadow ray) in place of a broadcast from the lower half and a block of masked
+//                     moves on the helpers.
+//   unmasked trace    when any lane has a ray the WHOLE wave runs the ray pass (a wave-uniform test, no saved exec mask and no masked
+//                     merge of the hit), and the shadow ray of a lane that does not step is left undefined instead of being set to
+//                     zeros and copies. The ray pass reads memory through scalar loads only (HELD: not at all), so a lane without a
+//                     ray computes garbage and touches nothing; `h` is read by lanes that traced, and by a PH_FLUSH step, which uses
+//                     hit.prim -- a record's index or -1 -- for an LDS address and selects everything else away.
+//   own film flush    w2_flush (below): the box filter and the tabulated filters in separate loop nests, the table read from LDS, so
+//                     that no wait inside a flush names vmcnt and the film's no-return atomics are never waited for (+1.0 % with the
+//                     box filter, -0.9 % with the Gaussian, where the atomics are the bound). The twin's three sites call v4_flush.
 // Not here: the step's component reads issued ahead of the ray pass, and components and shading record requested in one batch
 // (both built and measured: no gain and a loss, section 7a). The splat path keeps
 // film_put_channel's debug test (DRMLT_DEBUG bit 1 must go on working; one scalar compare per flushed splat).
 // stats[16] counts the waves that ran it (no build without stamps writes that slot; drmlt_stats_get prints it under DRMLT_VERBOSE).
+//
+// HELD (w2h; k_mutate_w2<false> is w2): the RAY PASS OVER RECORDS HELD IN VECTOR REGISTERS. A scene of one to three cuboids and at
+// most one flat record without plain triangles (bench.py's Cornell box: three cuboids and the light) has 58 dwords of records, which
+// never change during a launch. w2 streams them through two software-pipelined scalar loops in every iteration: the block's
+// pointers, then the records, counters, read-ahead and waits. w2h reads them once, in the prologue, pinned like W2Held, and the
+// pass is straight-line code that reads no memory at all (device_path.h: trace_held -- test_box and test_flat as they are, in the
+// loops' order, on the same values: the same chains bit for bit). launch_mutate runs it where the plan says so (launch_plan.h:
+// w2_held_launch; DRMLT_NO_W2_HELD keeps w2). Two more things are w2h's own, and nothing launches a mixed form, so the one parameter
+// selects them too: the decide is w2h_decide, by selects (w2: mh_decide and the twin's digest), and the step runs its emitter-hit block
+// only when a bounce ray of the wave hit the light (path_step_diffuse's RARE_EMITTER_HIT). stats[14..16] as w2, and stats[17] counts
+// the waves that ran w2h. The loop stands in the kernel itself, not in a routine both instantiations call: tools/isa_sections.py and
+// the tests of the build (tests/test_w2_flush_isa.py, test_w2h_isa.py, test_w2h_decide_isa.py) count instructions by the kernel's own lines.
+
 // the hand-off in one v_permlane32_swap per value: lane i < 32 keeps `keep`, lane 32 + i receives lane i's `give`
 DEV unsigned lower_keeps_u(unsigned keep, unsigned give) { return __builtin_amdgcn_permlane32_swap(keep, give, false, false)[0]; }
 DEV float lower_keeps(float keep, float give) { return __uint_as_float(lower_keeps_u(__float_as_uint(keep), __float_as_uint(give))); }
@@ -1111,323 +1118,13 @@ DEV void w2_flush(const DParams &P, const V4Lds &L, uint32_t &qn, uint32_t lane)
     }
     qn = 0u;
 }
-#ifndef W2_SHARED_FLUSH
-#define W2_FLUSH w2_flush
-#else
-#define W2_FLUSH v4_flush
-#endif
 
-#if defined(W2_NO_HELD_CONSTANTS) && !defined(W2_SCALARS_LOADED)
-#define W2_SCALARS_LOADED // (the scalars' vector copies sit beside W2Held)
-#endif
-#ifndef W2_NO_HELD_CONSTANTS
-#define W2_SECTION(name) const W2Held &name = held
-#else
-#define W2_SECTION(name) SECTION_PARAMS(name##_p); const W2Held name = w2_held(name##_p)
-#endif
-
-__global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_t n_mut, uint32_t mut_base) {
-    typedef RowSamplerT<RULE_ORBITAL> RowSampler;
-    if (threadIdx.x == 0) { atomicAdd(P.stats + 14, 1ull); atomicAdd(P.stats + 15, 1ull); atomicAdd(P.stats + 16, 1ull); }
-    const uint32_t lane = threadIdx.x;
-    const uint32_t sub = lane & 31u;
-    const bool helper = lane >= 32u;
-    const uint32_t c = blockIdx.x * 32u + sub;
-    const bool live = !helper && c < P.n_chains;
-    const uint32_t cc = c < P.n_chains ? c : P.n_chains - 1;
-    const uint32_t S = V4_STRIDE;
-    int smp_mode = SM_STAGE1;
-    uint32_t roles;
-    uint32_t qn = 0u;
-    ChainState cs;
-    float cum = 0.f;
-    Counters ct = {0u, 0u, 0u, 0u, 0u};
-    PathState ps;
-    bool helper_has_ray = false;
-    Hit h{-1, 0.f, 0.f, 0.f};
-    int batch;
-    uint32_t base = 0u, target = 0u, limit = 0u;
-    bool reported = false;
-#ifndef W2_NO_HELD_CONSTANTS
-    W2Held held = w2_held(P);
-    w2_hold(held);
-#endif
-#ifndef W2_SCALARS_LOADED
-    // (W2Held's companions: what the bookkeeping branch needs in SCALAR registers, one v_readfirstlane each where it opens)
-    uint32_t imp_lo = (uint32_t) (uintptr_t) P.importance, imp_hi = (uint32_t) ((uintptr_t) P.importance >> 32);
-    uint32_t done_lo = (uint32_t) (uintptr_t) P.chain_done, done_hi = (uint32_t) ((uintptr_t) P.chain_done >> 32);
-    uint32_t left_lo = (uint32_t) (uintptr_t) P.waves_left, left_hi = (uint32_t) ((uintptr_t) P.waves_left >> 32);
-    uint32_t key0_v = P.key0, key1_v = P.key1, chain_off_v = P.chain_offset, timid_v = (uint32_t) P.timid_after_large;
-    hold_v(imp_lo); hold_v(imp_hi); hold_v(done_lo); hold_v(done_hi); hold_v(left_lo); hold_v(left_hi);
-    hold_v(key0_v); hold_v(key1_v); hold_v(chain_off_v); hold_v(timid_v);
-#endif
-    { // the prologue of k_mutate_v4
-        const V4Layout<RULE_ORBITAL> Y = v4_layout<RULE_ORBITAL>(P, V4_QCAP);
-        roles = RowSampler::first_roles(Y.group, sub);
-        if (!helper) {
-            for (uint32_t k = 0; k < Y.D; ++k) lds_x[k * S + sub] = unwrap01(P.x[(size_t) k * P.n_chains + cc]);
-            for (uint32_t k = Y.D; k < Y.D4; ++k) lds_x[k * S + sub] = 0.f;
-        }
-        cs.cur.lum = P.cur_lum[cc]; cs.cur.px = P.cur_px[cc]; cs.cur.py = P.cur_py[cc];
-        cs.cur.r = P.cur_r[cc]; cs.cur.g = P.cur_g[cc]; cs.cur.b = P.cur_b[cc];
-        cs.y = cs.cur; cs.z = cs.cur;
-        cs.a1 = 0.f; cs.coin_acc1 = cs.coin_acc2 = cs.coin_mix = 0.f;
-        cs.it = 0u; cs.nd1 = cs.nd2 = 0u; cs.stage = -1; cs.large = false;
-        path_init(P, ps);
-        base = (P.chain_done && live) ? P.chain_done[cc] : mut_base;
-        target = P.chain_done ? n_mut : mut_base + n_mut;
-        limit = P.chain_done ? P.run_limit : target;
-        ps.phase = (live && base < limit) ? PH_DONE : PH_IDLE;
-        ps.o = mk3(0.f, 0.f, 0.f); ps.d = mk3(0.f, 0.f, 1.f); ps.tmin = 0.f; ps.tmax = 0.f;
-        batch = P.mh_batch > 32 ? 32 : P.mh_batch;
-        stage_tables(P, Y.LT, lane);
-        if (!helper) {
-            const u4 coins = philox4x32_10(P.key0, P.key1, 0u, base, P.chain_offset + blockIdx.x * 32u + sub, TAG_COIN);
-            float *dst = &lds_x[Y.L.coin_off + sub];
-            dst[0] = u32_to_unit(coins.x); dst[S] = u32_to_unit(coins.y); dst[2u * S] = u32_to_unit(coins.z); dst[3u * S] = u32_to_unit(coins.w);
-        }
-    }
-
-    for (;;) {
-        const bool parked = ps.phase == PH_DONE;
-        const unsigned long long pmask = __ballot(parked);
-        const unsigned long long rmask = __ballot(ps.phase != PH_DONE && ps.phase != PH_IDLE);
-        if (!pmask && !rmask) break;
-        if (pmask && (__popcll(pmask) >= batch || !rmask)) {
-            // the branch's scalars: what steers wave-uniform branches, loop bounds and scalar addresses (importance, timid_after_large,
-            // eff_dim, chain_done, waves_left) and the Philox keys -- one block for the whole branch
-#ifndef W2_SCALARS_LOADED
-            DParams Pm{};
-            Pm.importance = uniform_ptr<const float>(imp_lo, imp_hi); Pm.width = (int) wave_uniform((uint32_t) held.width); Pm.height = (int) wave_uniform((uint32_t) held.height);
-            Pm.chain_done = uniform_ptr<uint32_t>(done_lo, done_hi); Pm.waves_left = uniform_ptr<uint32_t>(left_lo, left_hi);
-            Pm.key0 = wave_uniform(key0_v); Pm.key1 = wave_uniform(key1_v); Pm.chain_offset = wave_uniform(chain_off_v);
-            Pm.eff_dim = (int) wave_uniform((uint32_t) held.eff_dim); Pm.timid_after_large = (int) wave_uniform(timid_v);
-            Pm.use_mixture = 0; Pm.acceptance_map = 0; Pm.type = 2; // (the orbital rule: mh_decide<RULE_ORBITAL> reads none of them)
-#else
-            SECTION_PARAMS(Pm);
-#endif
-            W2_SECTION(C);
-            const V4Lds L{C.coin_off, C.list_off, C.q_off, C.qcap};
-            RowSampler smp = w2_sampler(Pm.key0, Pm.key1);
-            smp.set_roles(roles, C.group, sub); smp.mode = smp_mode;
-            const uint32_t D4 = ((uint32_t) Pm.eff_dim + 3u) & ~3u, nb1 = D4 / 4u;
-            int *const lds_list = reinterpret_cast<int *>(&lds_x[L.list_off]);
-            __builtin_amdgcn_s_setprio(2);
-            if (qn + 64u > wave_uniform(L.qcap)) { SECTION_PARAMS(Pf); W2_FLUSH(Pf, L, qn, lane); }
-            // ---- decide (parked chain lanes), as k_mutate_v4: slot A = the current state when it is left, else y; slot B = y when
-            // z is adopted, else z
-            int commit = 0, kind = 0; // kind: 0 nothing / finished, 1 next mutation, 2 second stage
-            bool wantA = false, wantB = false;
-            float eAx = 0.f, eAy = 0.f, eAr = 0.f, eAg = 0.f, eAb = 0.f;
-            float eBx = 0.f, eBy = 0.f, eBr = 0.f, eBg = 0.f, eBb = 0.f;
-            if (parked) {
-                const MhDigest o = mh_decide<RULE_ORBITAL>(Pm, cs, smp, ps, ct);
-                if (o.decided) {
-                    cum += o.w.w0;
-                    const bool a1st = o.acc1, a2nd = o.acc2, adopt = a1st || a2nd;
-                    const DSplat sb = select_splat(a2nd, cs.y, cs.z);
-                    const float wb = a2nd ? o.w.w1 : o.w.w2;
-                    wantB = !a1st && wb > 0.f;
-                    eBx = sb.px; eBy = sb.py; eBr = sb.r * wb; eBg = sb.g * wb; eBb = sb.b * wb;
-                    const DSplat sa = select_splat(adopt, cs.cur, cs.y);
-                    const float wa = adopt ? cum : o.w.w1;
-                    wantA = wa > 0.f;
-                    eAx = sa.px; eAy = sa.py; eAr = sa.r * wa; eAg = sa.g * wa; eAb = sa.b * wa;
-                    if (adopt) {
-                        cum = a1st ? o.w.w1 : o.w.w2;
-                        cs.cur = select_splat(a1st, cs.y, cs.z);
-                    }
-                    commit = mh_commit_mode(o);
-                }
-                kind = cs.stage < 0 ? 4 : 2; // 4: between mutations -- resolved below
-            }
-            kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
-            v4_enqueue(L, qn, wantA, eAx, eAy, eAr, eAg, eAb);
-            v4_enqueue(L, qn, wantB, eBx, eBy, eBr, eBg, eBb);
-
-            // ---- commit: the chosen proposal's row group becomes the chain's x group
-            smp.adopt(commit);
-            roles = smp.roles();
-
-            // ---- start (parked chain lanes): the coins of the mutation that begins were drawn with the previous one
-            if (parked && kind == 1) {
-                const float *cn = &lds_x[L.coin_off + sub];
-                cs.large = cn[0] < C.p_large;
-                cs.coin_acc1 = cn[S]; cs.coin_acc2 = cn[2u * S]; cs.coin_mix = cn[3u * S];
-                cs.stage = 0;
-                cs.nd1 = cs.nd2 = 0u;
-            }
-
-            // ---- proposals of the chains that start a mutation, flattened: items (chain j, Philox block b) -> dimensions
-            // 4b..4b+3 of y; block nb1 = the four coins of the NEXT mutation
-            RowSampler smg = w2_sampler(Pm.key0, Pm.key1);
-            const uint32_t chain_base_g = Pm.chain_offset + blockIdx.x * 32u;
-            const uint32_t maj_mine = base + cs.it;
-            const unsigned info = roles | (cs.large ? 1u : 0u);
-            const uint32_t f1mask = (uint32_t) __ballot(kind == 1);
-            if (f1mask) {
-                if (kind == 1) lds_list[__builtin_amdgcn_mbcnt_lo(f1mask, 0u)] = (int) sub;
-                const uint32_t n = (uint32_t) __popc(f1mask), total = n * (nb1 + 1u);
-                const float rcp_n = 1.f / (float) n;
-                for (uint32_t fb = 0u; fb < total; fb += 64u) {
-                    const uint32_t i = fb + lane;
-                    const bool valid = i < total;
-                    const uint32_t ii = valid ? i : 0u;
-                    const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
-                    const uint32_t cj = (uint32_t) lds_list[j];
-                    const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
-                    const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
-                    smg.set_roles(inf, C.group, cj);
-#ifndef W2_TWO_PHILOX
-                    const bool coin = b >= nb1;
-                    if (valid) {
-                        const u4 r = philox4x32_10(Pm.key0, Pm.key1, coin ? 0u : b, coin ? mj + 1u : mj, chain_base_g + cj, coin ? TAG_COIN : TAG_S1);
-                        const Unit4 u{{u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)}};
-                        if (!coin) row_fill_first_drawn(smg, b, u, (inf & 1u) != 0u);
-                        else {
-                            float *dst = &lds_x[L.coin_off + cj];
-                            dst[0] = u.v[0]; dst[S] = u.v[1]; dst[2u * S] = u.v[2]; dst[3u * S] = u.v[3];
-                        }
-                    }
-#else
-                    if (valid) {
-                        if (b < nb1) smg.fill_first(b, mj, chain_base_g + cj, (inf & 1u) != 0u);
-                        else {
-                            const u4 coins = philox4x32_10(Pm.key0, Pm.key1, 0u, mj + 1u, chain_base_g + cj, TAG_COIN);
-                            float *dst = &lds_x[L.coin_off + cj];
-                            dst[0] = u32_to_unit(coins.x); dst[S] = u32_to_unit(coins.y); dst[2u * S] = u32_to_unit(coins.z); dst[3u * S] = u32_to_unit(coins.w);
-                        }
-                    }
-#endif
-                }
-            }
-            const uint32_t f2mask = (uint32_t) __ballot(kind == 2);
-            if (f2mask) { // second-stage proposals (rare: rejected bold steps)
-                if (kind == 2) lds_list[__builtin_amdgcn_mbcnt_lo(f2mask, 0u)] = (int) sub;
-                const uint32_t nb2 = Pm.timid_after_large ? D4 / 4u : (D4 / 2u + 3u) / 4u;
-                const uint32_t n = (uint32_t) __popc(f2mask), total = n * nb2;
-                const float rcp_n = 1.f / (float) n;
-                for (uint32_t fb = 0u; fb < total; fb += 64u) {
-                    const uint32_t i = fb + lane;
-                    const bool valid = i < total;
-                    const uint32_t ii = valid ? i : 0u;
-                    const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
-                    const uint32_t cj = (uint32_t) lds_list[j];
-                    const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
-                    const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
-                    smg.set_roles(inf, C.group, cj);
-                    if (valid) smg.fill_second(b, D4, mj, chain_base_g + cj, (inf & 1u) != 0u);
-                }
-            }
-
-            // ---- begin the evaluation (parked chain lanes): film position and camera ray from the first two components
-            if (parked) {
-                if (kind == 0) ps.phase = PH_IDLE;
-                else {
-                    DParams Vb{}; // what path_init and path_begin read of the block
-                    Vb.exclude_direct = C.exclude_direct; Vb.width = C.width; Vb.height = C.height;
-                    Vb.tan_half_fov = C.tan_half_fov; Vb.inv_aspect = C.inv_aspect; Vb.near_clip = C.near_clip; Vb.far_clip = C.far_clip;
-#pragma unroll
-                    for (int q = 0; q < 12; ++q) Vb.cam[q] = C.cam[q];
-                    smp_mode = smp.mode = cs.stage == 0 ? SM_STAGE1 : SM_STAGE2;
-                    path_init(Vb, ps);
-                    const float v0 = smp.next(0u), v1 = smp.next(1u);
-                    path_begin(Vb, ps, v0, v1);
-                }
-            }
-        }
-        // one ray per lane: chain lanes their camera / bounce ray, helpers the shadow ray they were handed
-        const bool tracing = helper ? helper_has_ray : ps.phase == PH_CLOSEST;
-        __builtin_amdgcn_s_setprio(0);
-        {
-            SECTION_PARAMS(Pt);
-#ifndef W2_MASKED_TRACE
-            if (__ballot(tracing)) h = trace<0>(Pt, ps.o, ps.d, ps.tmin, ps.tmax, helper); // every lane, whatever its ray: only lanes that traced read `h`
-#else
-            if (tracing) h = trace<0>(Pt, ps.o, ps.d, ps.tmin, ps.tmax, helper);
-#endif
-        }
-        __builtin_amdgcn_s_setprio(3);
-        const unsigned occluded = from_upper_u((helper_has_ray && h.prim >= 0) ? 1u : 0u);
-        helper_has_ray = false;
-        ShadowRay sr;
-#ifndef W2_MASKED_TRACE
-        asm volatile("" : "=v"(sr.d.x), "=v"(sr.d.y), "=v"(sr.d.z), "=v"(sr.tmin), "=v"(sr.tmax)); // whatever the registers hold: read under sr.valid only
-        sr.o = ps.o; sr.valid = false;
-#else
-        sr.o = ps.o; sr.d = ps.d; sr.tmin = 0.f; sr.tmax = 0.f; sr.valid = false;
-#endif
-        {
-            // no scalar load at the head of the step; its LDS reads still leave in three dependent trips (components, shading record, BSDF)
-            W2_SECTION(Cs);
-            if (!helper && ps.phase != PH_DONE && ps.phase != PH_IDLE) {
-                RowSampler sms = w2_sampler(0u, 0u);
-                sms.set_roles(roles, Cs.group, sub); sms.mode = smp_mode;
-                DParams Vs{}; // what path_step_diffuse reads of the block
-                Vs.eff_dim = Cs.eff_dim; Vs.rr_depth = Cs.rr_depth; Vs.max_depth = Cs.max_depth;
-                const LdsTables LT{Cs.shade_off, Cs.bsdf_off, 0u}; // (the emitter table is not read: HeldLightTables)
-#ifndef W2_MASKED_STEP
-                path_step_diffuse<RowSampler, HeldLightTables, false>(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
-#else
-                path_step_diffuse(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
-#endif
-            }
-        }
-        // hand the shadow ray of this vertex to the helper lane
-#ifndef W2_COPIED_HANDOFF
-        ps.o.x = lower_keeps(ps.o.x, sr.o.x); ps.o.y = lower_keeps(ps.o.y, sr.o.y); ps.o.z = lower_keeps(ps.o.z, sr.o.z);
-        ps.d.x = lower_keeps(ps.d.x, sr.d.x); ps.d.y = lower_keeps(ps.d.y, sr.d.y); ps.d.z = lower_keeps(ps.d.z, sr.d.z);
-        ps.tmin = lower_keeps(ps.tmin, sr.tmin); ps.tmax = lower_keeps(ps.tmax, sr.tmax);
-        helper_has_ray = lower_keeps_u(0u, sr.valid ? 1u : 0u) != 0u; // (a chain lane keeps the `false` set above)
-#else
-        const float ox = from_lower(sr.o.x), oy = from_lower(sr.o.y), oz = from_lower(sr.o.z);
-        const float dx = from_lower(sr.d.x), dy = from_lower(sr.d.y), dz = from_lower(sr.d.z);
-        const float t0 = from_lower(sr.tmin), t1 = from_lower(sr.tmax);
-        const float vf = from_lower(sr.valid ? 1.f : 0.f);
-        if (helper) {
-            ps.o = mk3(ox, oy, oz); ps.d = mk3(dx, dy, dz); ps.tmin = t0; ps.tmax = t1;
-            helper_has_ray = vf != 0.f;
-        }
-#endif
-    }
-    // the epilogue of k_mutate_v4, on its own copy of the block
-    SECTION_PARAMS(Pe);
-    const V4Layout<RULE_ORBITAL> Y = v4_layout<RULE_ORBITAL>(Pe, V4_QCAP);
-    if (qn + 32u > Y.L.qcap) W2_FLUSH(Pe, Y.L, qn, lane);
-    v4_enqueue(Y.L, qn, live && cum > 0.f, cs.cur.px, cs.cur.py, cs.cur.r * cum, cs.cur.g * cum, cs.cur.b * cum);
-    W2_FLUSH(Pe, Y.L, qn, lane);
-    if (live) {
-        RowSampler smp = Y.smp;
-        smp.set_roles(roles, Y.group, sub);
-        for (uint32_t k = 0; k < Y.D; ++k) Pe.x[(size_t) k * Pe.n_chains + c] = smp.x(k);
-        Pe.cur_lum[c] = cs.cur.lum; Pe.cur_px[c] = cs.cur.px; Pe.cur_py[c] = cs.cur.py;
-        Pe.cur_r[c] = cs.cur.r; Pe.cur_g[c] = cs.cur.g; Pe.cur_b[c] = cs.cur.b;
-        if (Pe.chain_done) Pe.chain_done[c] = base + cs.it;
-    }
-    if (Pe.chain_done && !reported && lane == 0) atomicSub(Pe.waves_left, 1u);
-    flush_counters(Pe, ct, lane);
-    const unsigned long long decided = wave_sum((live && !helper) ? cs.it : 0u);
-    if (lane == 0) atomicAdd(Pe.stats + 9, decided);
-}
-#undef W2_SECTION
-#undef W2_FLUSH
-
-// ------------------------------------------------------------------------------------------
-// k_mutate_w2h: k_mutate_w2 with the RAY PASS OVER RECORDS HELD IN VECTOR REGISTERS. A scene of one to three cuboids and at most
-// one flat record without plain triangles (bench.py's Cornell box: three cuboids and the light) has 58 dwords of records, which never
-// change during a launch. k_mutate_w2 streams them through two software-pipelined scalar loops in every iteration: the block's
-// pointers, then the records, counters, read-ahead and waits. Here they are read once, in the prologue, pinned like W2Held, and the
-// pass is straight-line code that reads no memory at all (device_path.h: trace_held -- test_box and test_flat as they are, in the
-// loops' order, on the same values: the same chains bit for bit). launch_mutate runs it where the plan says so (launch_plan.h:
-// w2_held_launch; DRMLT_NO_W2_HELD keeps k_mutate_w2). The loop is k_mutate_w2's in its default form, statement for statement,
-// but for two things of its own: the decide is w2h_decide, by selects (-DW2H_BRANCHED_DECIDE: k_mutate_w2's), and the step runs its
-// emitter-hit block only when a bounce ray of the wave hit the light (path_step_diffuse's RARE_EMITTER_HIT; -DW2H_EMITTER_HIT_ALWAYS).
-// A copy, not a template over both, because tests/test_w2_flush_isa.py pins k_mutate_w2's flush by the kernel's own call sites.
-// The flush sites call w2_flush by name. stats[14..16] as k_mutate_w2, and stats[17] counts the waves that ran this kernel.
+// the scene's ray records of k_mutate_w2<true>; k_mutate_w2<false> holds none
 struct W2HeldScene {
     HeldScene S;
     uint32_t counts; // n_box | n_flat_rec << 8
 };
+struct W2StreamedScene {};
 // the twelve floats of a record's rows, pinned one by one, then as the vector pairs the tests read
 template <class Rec> DEV void w2_hold_rows(Rec &G, const float *c, const float *rz, bool have) {
     float v[12];
@@ -1469,9 +1166,12 @@ DEV W2HeldScene w2_held_scene(const DParams &P) {
     return H;
 }
 
-__global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32_t n_mut, uint32_t mut_base) {
+template <bool HELD> __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2(DParams P, uint32_t n_mut, uint32_t mut_base) {
     typedef RowSamplerT<RULE_ORBITAL> RowSampler;
-    if (threadIdx.x == 0) { atomicAdd(P.stats + 14, 1ull); atomicAdd(P.stats + 15, 1ull); atomicAdd(P.stats + 16, 1ull); atomicAdd(P.stats + 17, 1ull); }
+    if (threadIdx.x == 0) {
+        atomicAdd(P.stats + 14, 1ull); atomicAdd(P.stats + 15, 1ull); atomicAdd(P.stats + 16, 1ull);
+        if constexpr (HELD) atomicAdd(P.stats + 17, 1ull);
+    }
     const uint32_t lane = threadIdx.x;
     const uint32_t sub = lane & 31u;
     const bool helper = lane >= 32u;
@@ -1493,7 +1193,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
     bool reported = false;
     W2Held held = w2_held(P);
     w2_hold(held);
-    const W2HeldScene scene = w2_held_scene(P);
+    typename std::conditional<HELD, W2HeldScene, W2StreamedScene>::type scene;
+    if constexpr (HELD) scene = w2_held_scene(P);
     // (W2Held's companions: what the bookkeeping branch needs in SCALAR registers, one v_readfirstlane each where it opens)
     uint32_t imp_lo = (uint32_t) (uintptr_t) P.importance, imp_hi = (uint32_t) ((uintptr_t) P.importance >> 32);
     uint32_t done_lo = (uint32_t) (uintptr_t) P.chain_done, done_hi = (uint32_t) ((uintptr_t) P.chain_done >> 32);
@@ -1534,7 +1235,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
         const unsigned long long rmask = __ballot(ps.phase != PH_DONE && ps.phase != PH_IDLE);
         if (!pmask && !rmask) break;
         if (pmask && (__popcll(pmask) >= batch || !rmask)) {
-            // the branch's scalars, as k_mutate_w2
+            // the branch's scalars: what steers wave-uniform branches, loop bounds and scalar addresses (importance, timid_after_large,
+            // eff_dim, chain_done, waves_left) and the Philox keys -- one block for the whole branch
             DParams Pm{};
             Pm.importance = uniform_ptr<const float>(imp_lo, imp_hi); Pm.width = (int) wave_uniform((uint32_t) held.width); Pm.height = (int) wave_uniform((uint32_t) held.height);
             Pm.chain_done = uniform_ptr<uint32_t>(done_lo, done_hi); Pm.waves_left = uniform_ptr<uint32_t>(left_lo, left_hi);
@@ -1549,31 +1251,23 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
             int *const lds_list = reinterpret_cast<int *>(&lds_x[L.list_off]);
             __builtin_amdgcn_s_setprio(2);
             if (qn + 64u > wave_uniform(L.qcap)) { SECTION_PARAMS(Pf); w2_flush(Pf, L, qn, lane); }
-            // ---- decide (parked chain lanes): by selects, no arm behind a divergent branch (w2h_decide)
+            // ---- decide (parked chain lanes). HELD: by selects, no arm behind a divergent branch (w2h_decide); else as k_mutate_v4
             int commit = 0, kind = 0; // kind: 0 nothing / finished, 1 next mutation, 2 second stage
-#ifndef W2H_BRANCHED_DECIDE
-            W2hQueued qa, qb;
-            w2h_decide(Pm, parked, cs, ps, ct, cum, commit, kind, qa, qb);
-            kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
-            v4_enqueue(L, qn, qa.want, qa.px, qa.py, qa.r, qa.g, qa.b);
-            v4_enqueue(L, qn, qb.want, qb.px, qb.py, qb.r, qb.g, qb.b);
-#else
-            bool wantA = false, wantB = false;
-            float eAx = 0.f, eAy = 0.f, eAr = 0.f, eAg = 0.f, eAb = 0.f;
-            float eBx = 0.f, eBy = 0.f, eBr = 0.f, eBg = 0.f, eBb = 0.f;
-            if (parked) {
+            W2hQueued qa{false, 0.f, 0.f, 0.f, 0.f, 0.f}, qb{false, 0.f, 0.f, 0.f, 0.f, 0.f};
+            if constexpr (HELD) w2h_decide(Pm, parked, cs, ps, ct, cum, commit, kind, qa, qb);
+            else if (parked) { // as k_mutate_v4: slot A = the current state when it is left, else y; slot B = y when z is adopted, else z
                 const MhDigest o = mh_decide<RULE_ORBITAL>(Pm, cs, smp, ps, ct);
                 if (o.decided) {
                     cum += o.w.w0;
                     const bool a1st = o.acc1, a2nd = o.acc2, adopt = a1st || a2nd;
                     const DSplat sb = select_splat(a2nd, cs.y, cs.z);
                     const float wb = a2nd ? o.w.w1 : o.w.w2;
-                    wantB = !a1st && wb > 0.f;
-                    eBx = sb.px; eBy = sb.py; eBr = sb.r * wb; eBg = sb.g * wb; eBb = sb.b * wb;
+                    qb.want = !a1st && wb > 0.f;
+                    qb.px = sb.px; qb.py = sb.py; qb.r = sb.r * wb; qb.g = sb.g * wb; qb.b = sb.b * wb;
                     const DSplat sa = select_splat(adopt, cs.cur, cs.y);
                     const float wa = adopt ? cum : o.w.w1;
-                    wantA = wa > 0.f;
-                    eAx = sa.px; eAy = sa.py; eAr = sa.r * wa; eAg = sa.g * wa; eAb = sa.b * wa;
+                    qa.want = wa > 0.f;
+                    qa.px = sa.px; qa.py = sa.py; qa.r = sa.r * wa; qa.g = sa.g * wa; qa.b = sa.b * wa;
                     if (adopt) {
                         cum = a1st ? o.w.w1 : o.w.w2;
                         cs.cur = select_splat(a1st, cs.y, cs.z);
@@ -1583,9 +1277,9 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
                 kind = cs.stage < 0 ? 4 : 2; // 4: between mutations -- resolved below
             }
             kind = mh_resolve_kind(Pm, kind, live, base + cs.it, target, limit, reported, lane);
-            v4_enqueue(L, qn, wantA, eAx, eAy, eAr, eAg, eAb);
-            v4_enqueue(L, qn, wantB, eBx, eBy, eBr, eBg, eBb);
-#endif
+            v4_enqueue(L, qn, qa.want, qa.px, qa.py, qa.r, qa.g, qa.b);
+            v4_enqueue(L, qn, qb.want, qb.px, qb.py, qb.r, qb.g, qb.b);
+
 
             // ---- commit: the chosen proposal's row group becomes the chain's x group
             smp.adopt(commit);
@@ -1668,12 +1362,17 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
         }
         // one ray per lane: chain lanes their camera / bounce ray, helpers the shadow ray they were handed. When any lane has a ray
         // the whole wave runs the pass, whatever its lanes hold: registers in, registers out, and only lanes that traced read `h`
-        // (a PH_FLUSH step reads hit.prim, a held record's index or -1, and selects everything else away).
+        // (a PH_FLUSH step reads hit.prim, a record's index or -1, and selects everything else away).
         const bool tracing = helper ? helper_has_ray : ps.phase == PH_CLOSEST;
         __builtin_amdgcn_s_setprio(0);
-        if (__ballot(tracing)) {
-            const uint32_t counts = wave_uniform(scene.counts);
-            h = trace_held(scene.S, counts & 0xffu, counts >> 8, ps.o, ps.d, ps.tmin, ps.tmax);
+        if constexpr (HELD) {
+            if (__ballot(tracing)) {
+                const uint32_t counts = wave_uniform(scene.counts);
+                h = trace_held(scene.S, counts & 0xffu, counts >> 8, ps.o, ps.d, ps.tmin, ps.tmax);
+            }
+        } else {
+            SECTION_PARAMS(Pt);
+            if (__ballot(tracing)) h = trace<0>(Pt, ps.o, ps.d, ps.tmin, ps.tmax, helper);
         }
         __builtin_amdgcn_s_setprio(3);
         const unsigned occluded = from_upper_u((helper_has_ray && h.prim >= 0) ? 1u : 0u);
@@ -1682,6 +1381,7 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
         asm volatile("" : "=v"(sr.d.x), "=v"(sr.d.y), "=v"(sr.d.z), "=v"(sr.tmin), "=v"(sr.tmax)); // whatever the registers hold: read under sr.valid only
         sr.o = ps.o; sr.valid = false;
         {
+            // no scalar load at the head of the step; its LDS reads still leave in three dependent trips (components, shading record, BSDF)
             const W2Held &Cs = held;
             if (!helper && ps.phase != PH_DONE && ps.phase != PH_IDLE) {
                 RowSampler sms = w2_sampler(0u, 0u);
@@ -1689,12 +1389,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
                 DParams Vs{}; // what path_step_diffuse reads of the block
                 Vs.eff_dim = Cs.eff_dim; Vs.rr_depth = Cs.rr_depth; Vs.max_depth = Cs.max_depth;
                 const LdsTables LT{Cs.shade_off, Cs.bsdf_off, 0u}; // (the emitter table is not read: HeldLightTables)
-#ifndef W2H_EMITTER_HIT_ALWAYS
-                constexpr bool RARE_HIT = true; // the emitter-hit block only in an iteration in which a bounce ray hit the light
-#else
-                constexpr bool RARE_HIT = false;
-#endif
-                path_step_diffuse<RowSampler, HeldLightTables, false, RARE_HIT>(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
+                // (RARE_EMITTER_HIT = HELD: w2h runs the emitter-hit block only in an iteration in which a bounce ray hit the light)
+                path_step_diffuse<RowSampler, HeldLightTables, false, HELD>(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
             }
         }
         // hand the shadow ray of this vertex to the helper lane
@@ -1703,7 +1399,8 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_w2h(DParams P, uint32
         ps.tmin = lower_keeps(ps.tmin, sr.tmin); ps.tmax = lower_keeps(ps.tmax, sr.tmax);
         helper_has_ray = lower_keeps_u(0u, sr.valid ? 1u : 0u) != 0u; // (a chain lane keeps the `false` set above)
     }
-    // the epilogue of k_mutate_v4, on its own copy of the block
+    // the epilogue of k_mutate_v4, on its own copy of the block; the last splat goes through this kernel's flush, called here by name
+    // (the tests of the build find a flush's instructions by the kernel's line that called it)
     SECTION_PARAMS(Pe);
     const V4Layout<RULE_ORBITAL> Y = v4_layout<RULE_ORBITAL>(Pe, V4_QCAP);
     if (qn + 32u > Y.L.qcap) w2_flush(Pe, Y.L, qn, lane);
@@ -2356,8 +2053,8 @@ void launch_mutate(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint
     // one-light twin when the scene has one light)
     case Build::V4_F0_STAMPS: LAUNCH_LIGHT(true, true);
     case Build::V4_F0: // (k_mutate_w2: the orbital one-light twin for launches without a third wave per SIMD -- plan.w2, launch_plan.h)
-        if (plan.w2_held && orbital && one_light) { LAUNCH(k_mutate_w2h); } // (its ray records in registers: plan.w2_held)
-        if (plan.w2 && orbital && one_light) { LAUNCH(k_mutate_w2); }
+        if (plan.w2_held && orbital && one_light) { LAUNCH(k_mutate_w2<true>); } // (its ray records in registers: plan.w2_held)
+        if (plan.w2 && orbital && one_light) { LAUNCH(k_mutate_w2<false>); }
         LAUNCH_LIGHT(true, false);
     case Build::V4_F3_STAMPS: LAUNCH(k_mutate_v4<3, true, true>); case Build::V4_F3: LAUNCH_RULE(3, true, false); case Build::V4_F7: LAUNCH_RULE(7, true, false);
     case Build::V4_F15_S32: LAUNCH(k_mutate_v4<15, true, false, false, true>); case Build::V4_F15_OVF: LAUNCH(k_mutate_v4<15, true, false, true, true>);

@@ -6,7 +6,7 @@ import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOL = "_Z11k_mutate_w27DParamsjj"
+SYMBOL = "_Z11k_mutate_w2ILb0EEv7DParamsjj"  # k_mutate_w2<false>, the streaming instantiation of the template
 KEYS = ("VGPRs", "AGPRs", "SGPRs Spill", "VGPRs Spill", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]")
 
 

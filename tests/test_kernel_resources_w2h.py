@@ -3,10 +3,11 @@ is k_mutate_w2 plus the scene's ray records in vector registers, 58 dwords and a
 and may use their whole register file -- 256 registers per lane, vector and accumulator registers together -- but nothing may
 spill and nothing may sit in scratch memory (a spilled record would be re-read from memory in the pass that holds it in order
 not to read memory). As measured on the commit that adds this file: 252 VGPRs, no AGPRs, no spilled scalar.
-k_mutate_w2 itself keeps what it had: the new kernel stands beside it and its text is untouched."""
+k_mutate_w2h is k_mutate_w2<true>, k_mutate_w2 the streaming instantiation k_mutate_w2<false> of the same template: the latter
+keeps the resources it had as a kernel of its own."""
 from test_kernel_resources_w2 import SYMBOL as W2_SYMBOL, remarks
 
-SYMBOL = "_Z12k_mutate_w2h7DParamsjj"
+SYMBOL = "_Z11k_mutate_w2ILb1EEv7DParamsjj"
 
 
 def test_two_waves_per_simd_without_spills(native_lib):

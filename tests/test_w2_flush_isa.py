@@ -23,6 +23,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import isa_waits  # noqa: E402
 
 FLUSH_SITES = 3  # the bookkeeping branch's and the epilogue's two
+SYMBOL = "_Z11k_mutate_w2ILb0EEv7DParamsjj"  # k_mutate_w2<false>: the source name alone matches both instantiations
+KERNEL_HEAD = " k_mutate_w2(DParams P,"     # the template's __global__ line in kernels.hip
 
 
 def routine_lines(src, head):
@@ -46,11 +48,13 @@ def flush_asm(tmp_path_factory):
     passes = routine_lines(src, "template <bool BOX> DEV void w2_flush_passes(")
     flush = routine_lines(src, "DEV void w2_flush(")
     assert put[1] < passes[0] and passes[1] < flush[0], "the pass loops' routines stand together, in front of w2_flush"
-    sites = [i + 1 for i, l in enumerate(src) if re.search(r"\bW2_FLUSH\(", l)]
+    first = next(i for i, l in enumerate(src) if "__global__" in l and KERNEL_HEAD in l)
+    last = next(i for i in range(first, len(src)) if src[i] == "}")
+    sites = [i + 1 for i in range(first, last) if re.search(r"\bw2_flush\(", src[i])]  # the kernel's own calls
     assert len(sites) == FLUSH_SITES, sites
     ranges = {"passes": (put[0], passes[1]), "staging": flush}
     print("source lines:", ranges, "flush sites:", sites)
-    return isa_waits.scan(open(out).read(), "k_mutate_w2", "kernels.hip", ranges), sites
+    return isa_waits.scan(open(out).read(), SYMBOL, "kernels.hip", ranges), sites
 
 
 def test_no_wait_for_the_atomics_inside_the_pass_loops(flush_asm):

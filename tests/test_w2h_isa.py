@@ -27,7 +27,8 @@ TOOLS = os.path.join(ROOT, "tools")
 sys.path.insert(0, TOOLS)
 import isa_waits  # noqa: E402
 
-SYMBOL = "_Z12k_mutate_w2h7DParamsjj"
+SYMBOL = "_Z11k_mutate_w2ILb1EEv7DParamsjj"  # k_mutate_w2<true>
+KERNEL_HEAD = " k_mutate_w2(DParams P,"     # the template's __global__ line in kernels.hip
 FLUSH_SITES = 3  # the bookkeeping branch's and the epilogue's two
 LOADS = ("s_load", "s_buffer_load", "flat_load", "global_load", "buffer_load", "scratch_load")
 RCPS = 3 * 3 + 1  # test_box: one per slab; test_flat: one
@@ -43,7 +44,7 @@ def build(tmp_path_factory):
                         "-gline-tables-only", "-o", out, "kernels.hip"], cwd=CSRC, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
     src = open(os.path.join(CSRC, "kernels.hip")).read().split("\n")
-    first = next(i for i, l in enumerate(src) if l.startswith("__global__") and " k_mutate_w2h(" in l)
+    first = next(i for i, l in enumerate(src) if "__global__" in l and KERNEL_HEAD in l)
     last = next(i for i in range(first, len(src)) if src[i] == "}")
     return dict(asm=out, text=open(out).read(), src=src, kernel=(first + 1, last + 1))
 
@@ -64,7 +65,7 @@ def test_ray_pass_by_source_lines(build):
 
 
 def test_ray_pass_by_the_assembly_text(build):
-    body = [l.split(";", 1)[0].strip() for l in isa_waits.kernel_body(build["text"].split("\n"), "k_mutate_w2h")]
+    body = [l.split(";", 1)[0].strip() for l in isa_waits.kernel_body(build["text"].split("\n"), SYMBOL)]
     ins = [t for t in body if t and not t.startswith((".", "//")) and not t.endswith(":")]
     lo = [i for i, t in enumerate(ins) if re.match(r"s_setprio\s+0\b", t)]
     hi = [i for i, t in enumerate(ins) if re.match(r"s_setprio\s+3\b", t)]
@@ -84,7 +85,7 @@ def test_flush_as_k_mutate_w2s(build):
     flush = routine_lines(src, "DEV void w2_flush(")
     sites = [i + 1 for i in range(first - 1, last) if re.search(r"\bw2_flush\(", src[i])]
     assert len(sites) == FLUSH_SITES, sites
-    res = isa_waits.scan(build["text"], "k_mutate_w2h", "kernels.hip", {"passes": (put[0], passes[1]), "staging": flush})
+    res = isa_waits.scan(build["text"], SYMBOL, "kernels.hip", {"passes": (put[0], passes[1]), "staging": flush})
     c = res["passes"]
     print(dict((k, v) for k, v in c.items() if k != "where"), c["where"])
     assert c["vmem_atomic"] == 2 * FLUSH_SITES
