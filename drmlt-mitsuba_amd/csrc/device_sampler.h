@@ -359,6 +359,37 @@ template <int RULE> DEV void row_fill_first_drawn(const RowSamplerT<RULE> &s, ui
     first_stage_block(RowSamplerT<RULE>::orbital ? 2 : s.type, large, u, x4, y);
     ys[0] = y[0]; ys[s.stride] = y[1]; ys[2u * s.stride] = y[2]; ys[3u * s.stride] = y[3];
 }
+// ONE PAIR of RowSamplerT::fill_second (orbital rule), the block's uniforms drawn by the CALLER (k_mutate_w2<true>: its one Philox
+// site serves second-stage items too, and an item is (chain, block b, pair p of the block's four) -- the four items of a block draw
+// the same block and each takes its own uniform): the same block rule, the same reads (row 0's for a pair beyond D4), the same
+// orbital_second_pair on the same values, the same stores to the same rows. Straight-line code: four reads, ONE wait, the rotation
+// on every lane that enters (a large step's item rotates whatever its rows hold), and only the stores are conditional -- a store
+// for a pair beyond D4 is never issued: the rows behind a group are the next group's, or the coin rows. A large step
+// (timidAfterLarge) stores the block's four uniforms to rows 4b .. 4b+3 through its pairs 0 and 1.
+template <int RULE> DEV void row_fill_second_pair_drawn(const RowSamplerT<RULE> &s, uint32_t b, uint32_t p, uint32_t D4, const Unit4 &u, bool large) {
+    static_assert(RowSamplerT<RULE>::orbital, "the orbital arm of fill_second");
+    const uint32_t nblk = large ? D4 / 4u : (D4 / 2u + 3u) / 4u;
+    const uint32_t k0 = 2u * (4u * b + p), kk = k0 + 1u < D4 ? k0 : 0u;
+    float xa = lds_x[s.x_off + kk * s.stride], xb = lds_x[s.x_off + (kk + 1u) * s.stride];
+    float ya = s.y_raw(kk), yb = s.y_raw(kk + 1u);
+    asm volatile("" : "+v"(xa), "+v"(xb), "+v"(ya), "+v"(yb)); // (every read has arrived here)
+    const bool hi = (p & 2u) != 0u, odd = (p & 1u) != 0u;
+    // (values, not loads: a select between two loads of the struct's fields becomes a load through a selected ADDRESS, and the struct
+    // then lives in scratch memory -- see PoolRowSampler::y_raw)
+    float u0 = u.v[0], u1 = u.v[1], u2 = u.v[2], u3 = u.v[3];
+    asm volatile("" : "+v"(u0), "+v"(u1), "+v"(u2), "+v"(u3));
+    const float xi = hi ? (odd ? u3 : u2) : (odd ? u1 : u0); // the pair's angle: draw p
+    const float la = odd ? u2 : u0, lb = odd ? u3 : u1;     // a large step's rows 4b + 2p, 4b + 2p + 1: draws 2p, 2p + 1 (p < 2)
+    float z0, z1;
+    orbital_second_pair(xi, wrap01(xa), wrap01(xb), ya, yb, z0, z1);
+    asm volatile("" : "+v"(z0), "+v"(z1)); // (... and the rotation is done here, not behind the stores' exec mask)
+    const bool put = b < nblk && (large ? !hi : k0 + 1u < D4);
+    const uint32_t zo = s.z_off(), row = large ? 4u * b + 2u * p : k0;
+    if (put) {
+        lds_x[zo + row * s.stride] = large ? la : z0;
+        lds_x[zo + (row + 1u) * s.stride] = large ? lb : z1;
+    }
+}
 
 // ------------------------------------------------------------------ PSS sampler of k_mutate_v5
 // Where a wave's proposal rows live. RowsLds: 64 columns of lds_x (one per chain of the wave). RowsMem: device memory, [dim][chain]

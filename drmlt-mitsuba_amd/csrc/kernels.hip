@@ -1015,11 +1015,11 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(
 // pointers, then the records, counters, read-ahead and waits. w2h reads them once, in the prologue, pinned like W2Held, and the
 // pass is straight-line code that reads no memory at all (device_path.h: trace_held -- test_box and test_flat as they are, in the
 // loops' order, on the same values: the same chains bit for bit). launch_mutate runs it where the plan says so (launch_plan.h:
-// w2_held_launch; DRMLT_NO_W2_HELD keeps w2). Two more things are w2h's own, and nothing launches a mixed form, so the one parameter
-// selects them too: the decide is w2h_decide, by selects (w2: mh_decide and the twin's digest), and the step runs its emitter-hit block
-// only when a bounce ray of the wave hit the light (path_step_diffuse's RARE_EMITTER_HIT). stats[14..16] as w2, and stats[17] counts
-// the waves that ran w2h. The loop stands in the kernel itself, not in a routine both instantiations call: tools/isa_sections.py and
-// the tests of the build (tests/test_w2_flush_isa.py, test_w2h_isa.py, test_w2h_decide_isa.py) count instructions by the kernel's own lines.
+// w2_held_launch; DRMLT_NO_W2_HELD keeps w2). Three more things are w2h's own, and nothing launches a mixed form, so the one parameter
+// selects them too: the decide is w2h_decide, by selects (w2: mh_decide and the twin's digest); the step runs its emitter-hit block only when
+// a bounce ray of the wave hit the light (RARE_EMITTER_HIT); and the proposals of both stages are filled in ONE flattened pass with one Philox
+// site (w2: two loops). stats[14..16] as w2, stats[17] counts w2h's waves. The loop stands in the kernel itself, not in a routine both call:
+// the tests of the build (tests/test_w2_flush_isa.py, test_w2h_isa.py, test_w2h_decide_isa.py, test_w2h_fill_isa.py) count by the kernel's lines.
 
 // the hand-off in one v_permlane32_swap per value: lane i < 32 keeps `keep`, lane 32 + i receives lane i's `give`
 DEV unsigned lower_keeps_u(unsigned keep, unsigned give) { return __builtin_amdgcn_permlane32_swap(keep, give, false, false)[0]; }
@@ -1300,47 +1300,95 @@ template <bool HELD> __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_
             const uint32_t maj_mine = base + cs.it;
             const unsigned info = roles | (cs.large ? 1u : 0u);
             const uint32_t f1mask = (uint32_t) __ballot(kind == 1);
-            if (f1mask) {
-                if (kind == 1) lds_list[__builtin_amdgcn_mbcnt_lo(f1mask, 0u)] = (int) sub;
-                const uint32_t n = (uint32_t) __popc(f1mask), total = n * (nb1 + 1u);
-                const float rcp_n = 1.f / (float) n;
-                for (uint32_t fb = 0u; fb < total; fb += 64u) {
-                    const uint32_t i = fb + lane;
-                    const bool valid = i < total;
-                    const uint32_t ii = valid ? i : 0u;
-                    const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
-                    const uint32_t cj = (uint32_t) lds_list[j];
-                    const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
-                    const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
-                    smg.set_roles(inf, C.group, cj);
-                    const bool coin = b >= nb1;
-                    if (valid) {
-                        const u4 r = philox4x32_10(Pm.key0, Pm.key1, coin ? 0u : b, coin ? mj + 1u : mj, chain_base_g + cj, coin ? TAG_COIN : TAG_S1);
-                        const Unit4 u{{u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)}};
-                        if (!coin) row_fill_first_drawn(smg, b, u, (inf & 1u) != 0u);
-                        else {
-                            float *dst = &lds_x[L.coin_off + cj];
-                            dst[0] = u.v[0]; dst[S] = u.v[1]; dst[2u * S] = u.v[2]; dst[3u * S] = u.v[3];
+            if constexpr (HELD) {
+                // w2h: ONE flattened pass. Items [0, t1) are the first-stage and coin items of the n1 chains that start a mutation, in
+                // k_mutate_w2's mapping (block b, chain j); behind them come the second-stage items of the n2 chains whose first stage
+                // was rejected -- typically one chain --, ONE PAIR each: item q = 4 b + p of chain j is pair p of Philox block b, so that
+                // they ride in the empty lanes of the last trip and the wave pays one rotation for them, not four. The list holds the
+                // first kind's columns in [0, n1) and the second's behind them (a chain has one kind: n1 + n2 <= 32). An item draws
+                // ONE Philox block at an address selected per lane (the four pairs of a block draw it four times: the lanes are
+                // there); what it does with the uniforms is its tail, and the second-stage tail (row_fill_second_pair_drawn) is
+                // entered only by a trip that holds such an item.
+                const uint32_t f2mask = (uint32_t) __ballot(kind == 2);
+                if (f1mask | f2mask) {
+                    const uint32_t n1 = (uint32_t) __popc(f1mask), n2 = (uint32_t) __popc(f2mask);
+                    if (kind == 1 || kind == 2) lds_list[kind == 1 ? __builtin_amdgcn_mbcnt_lo(f1mask, 0u) : n1 + __builtin_amdgcn_mbcnt_lo(f2mask, 0u)] = (int) sub;
+                    const uint32_t nb2 = Pm.timid_after_large ? D4 / 4u : (D4 / 2u + 3u) / 4u;
+                    const uint32_t t1 = n1 * (nb1 + 1u), total = t1 + n2 * 4u * nb2;
+                    for (uint32_t fb = 0u; fb < total; fb += 64u) {
+                        const uint32_t i = fb + lane;
+                        const bool valid = i < total, second = valid && i >= t1;
+                        const uint32_t ii = valid ? (second ? i - t1 : i) : 0u, n = second ? n2 : n1;
+                        // (the reciprocal per lane, by v_rcp: (ii + 0.5) / n is at least 1/64 from a whole number, one ulp does not move its
+                        // floor, and a select between two quotients made in front of the loop compiles to a full division in every trip.
+                        // n == 0 only on lanes without an item)
+                        const uint32_t q = (uint32_t) (((float) ii + 0.5f) * __builtin_amdgcn_rcpf((float) n)), j = ii - q * n;
+                        const uint32_t b = second ? q >> 2 : q;
+                        const uint32_t cj = (uint32_t) lds_list[second ? n1 + j : j];
+                        const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
+                        const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
+                        smg.set_roles(inf, C.group, cj);
+                        const bool coin = !second && b >= nb1;
+                        Unit4 u{{0.f, 0.f, 0.f, 0.f}};
+                        if (valid) {
+                            const u4 r = philox4x32_10(Pm.key0, Pm.key1, coin ? 0u : b, coin ? mj + 1u : mj, chain_base_g + cj, coin ? TAG_COIN : (second ? TAG_S2 : TAG_S1));
+                            u = Unit4{{u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)}};
+                            if (!second) {
+                                if (!coin) row_fill_first_drawn(smg, b, u, (inf & 1u) != 0u);
+                                else {
+                                    float *dst = &lds_x[L.coin_off + cj];
+                                    dst[0] = u.v[0]; dst[S] = u.v[1]; dst[2u * S] = u.v[2]; dst[3u * S] = u.v[3];
+                                }
+                            }
+                        }
+                        if (__ballot(second)) {
+                            if (second) row_fill_second_pair_drawn(smg, b, q & 3u, D4, u, (inf & 1u) != 0u);
                         }
                     }
                 }
-            }
-            const uint32_t f2mask = (uint32_t) __ballot(kind == 2);
-            if (f2mask) { // second-stage proposals (rare: rejected bold steps)
-                if (kind == 2) lds_list[__builtin_amdgcn_mbcnt_lo(f2mask, 0u)] = (int) sub;
-                const uint32_t nb2 = Pm.timid_after_large ? D4 / 4u : (D4 / 2u + 3u) / 4u;
-                const uint32_t n = (uint32_t) __popc(f2mask), total = n * nb2;
-                const float rcp_n = 1.f / (float) n;
-                for (uint32_t fb = 0u; fb < total; fb += 64u) {
-                    const uint32_t i = fb + lane;
-                    const bool valid = i < total;
-                    const uint32_t ii = valid ? i : 0u;
-                    const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
-                    const uint32_t cj = (uint32_t) lds_list[j];
-                    const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
-                    const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
-                    smg.set_roles(inf, C.group, cj);
-                    if (valid) smg.fill_second(b, D4, mj, chain_base_g + cj, (inf & 1u) != 0u);
+            } else {
+                if (f1mask) {
+                    if (kind == 1) lds_list[__builtin_amdgcn_mbcnt_lo(f1mask, 0u)] = (int) sub;
+                    const uint32_t n = (uint32_t) __popc(f1mask), total = n * (nb1 + 1u);
+                    const float rcp_n = 1.f / (float) n;
+                    for (uint32_t fb = 0u; fb < total; fb += 64u) {
+                        const uint32_t i = fb + lane;
+                        const bool valid = i < total;
+                        const uint32_t ii = valid ? i : 0u;
+                        const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
+                        const uint32_t cj = (uint32_t) lds_list[j];
+                        const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
+                        const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
+                        smg.set_roles(inf, C.group, cj);
+                        const bool coin = b >= nb1;
+                        if (valid) {
+                            const u4 r = philox4x32_10(Pm.key0, Pm.key1, coin ? 0u : b, coin ? mj + 1u : mj, chain_base_g + cj, coin ? TAG_COIN : TAG_S1);
+                            const Unit4 u{{u32_to_unit(r.x), u32_to_unit(r.y), u32_to_unit(r.z), u32_to_unit(r.w)}};
+                            if (!coin) row_fill_first_drawn(smg, b, u, (inf & 1u) != 0u);
+                            else {
+                                float *dst = &lds_x[L.coin_off + cj];
+                                dst[0] = u.v[0]; dst[S] = u.v[1]; dst[2u * S] = u.v[2]; dst[3u * S] = u.v[3];
+                            }
+                        }
+                    }
+                }
+                const uint32_t f2mask = (uint32_t) __ballot(kind == 2);
+                if (f2mask) { // second-stage proposals (rare: rejected bold steps)
+                    if (kind == 2) lds_list[__builtin_amdgcn_mbcnt_lo(f2mask, 0u)] = (int) sub;
+                    const uint32_t nb2 = Pm.timid_after_large ? D4 / 4u : (D4 / 2u + 3u) / 4u;
+                    const uint32_t n = (uint32_t) __popc(f2mask), total = n * nb2;
+                    const float rcp_n = 1.f / (float) n;
+                    for (uint32_t fb = 0u; fb < total; fb += 64u) {
+                        const uint32_t i = fb + lane;
+                        const bool valid = i < total;
+                        const uint32_t ii = valid ? i : 0u;
+                        const uint32_t b = (uint32_t) (((float) ii + 0.5f) * rcp_n), j = ii - b * n;
+                        const uint32_t cj = (uint32_t) lds_list[j];
+                        const uint32_t mj = (uint32_t) __shfl((int) maj_mine, (int) cj, 64);
+                        const unsigned inf = (unsigned) __shfl((int) info, (int) cj, 64);
+                        smg.set_roles(inf, C.group, cj);
+                        if (valid) smg.fill_second(b, D4, mj, chain_base_g + cj, (inf & 1u) != 0u);
+                    }
                 }
             }
 
