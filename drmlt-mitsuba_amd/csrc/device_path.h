@@ -96,7 +96,9 @@ template <int FEAT = 15> DEV void intersect_prim(const DPrim &P, int idx, f3 o, 
         // The kind is wave-uniform (SGPR), so this is selects on a scalar condition, no exec-mask traffic.
         const bool tri = P.type == PRIM_TRIANGLE;
         const float w = tri ? 1.f - (u + v) : fminf(1.f - u, 1.f - v);
-        bool hit = fminf(fminf(u, v), w) >= 0.f && t >= tmin && t <= h.t;
+        // (w >= 0 on its own: a ray parallel to the plane has t = +inf, which passes t <= h.t for a ray without a far end; where one of
+        // the rows u, v is orthogonal to it too, that coordinate and a triangle's w are inf * 0 = NaN, and fminf skips a NaN)
+        bool hit = fminf(fminf(u, v), w) >= 0.f && w >= 0.f && t >= tmin && t <= h.t;
         int id = idx;
         if (P.type == PRIM_QUAD2) { // sub-triangle (a,b,c) for v <= u, (a,c,d) otherwise; its own barycentrics
             const bool second = v > u;
@@ -144,7 +146,7 @@ template <int FEAT = 15> DEV void intersect_leaf(const DPrim &P, bool ok, f3 o, 
     const float u = fmaf(t, ld.x, lo.x), v = fmaf(t, ld.y, lo.y);
     const float w_tri = 1.f - (u + v), w_par = fminf(1.f - u, 1.f - v);
     const float w = type == PRIM_TRIANGLE ? w_tri : w_par;
-    bool hit = ok & (fminf(fminf(u, v), w) >= 0.f) & (t >= tmin) & (t <= h.t);
+    bool hit = ok & (fminf(fminf(u, v), w) >= 0.f) & (w >= 0.f) & (t >= tmin) & (t <= h.t); // (w >= 0: intersect_prim has the reason)
     if (FEAT & 4) hit = hit & (type != PRIM_SPHERE);
     const bool quad2 = type == PRIM_QUAD2, second = quad2 & (v > u); // sub-triangle (a,b,c) for v <= u, (a,c,d) otherwise; its own barycentrics
     const float uq = second ? u : u - v, vq = second ? v - u : v;
@@ -445,7 +447,11 @@ template <bool TRI> DEV void test_flat(const FlatRec &G, f3 o, f3 d, float tmin,
     float w;
     if (TRI && (G.ks & 0xff) == PRIM_TRIANGLE) w = 1.f - (uv.x + uv.y);
     else { const float2v om = 1.f - uv; w = fminf(om.x, om.y); }
-    const bool hit = fminf(fminf(uv.x, uv.y), w) >= 0.f && t >= tmin && t <= best_t;
+    bool hit = fminf(fminf(uv.x, uv.y), w) >= 0.f && t >= tmin && t <= best_t;
+    // a triangle's w can be NaN behind a non-negative minimum (intersect_prim has the reason). A parallelogram's cannot: the rows u, v and the
+    // normal's span space, so a direction orthogonal to the normal's row and to one of u, v is not orthogonal to the other; that coordinate is
+    // +-inf at t = +inf, and it or its 1 - x fails the test
+    if (TRI) hit = hit && w >= 0.f;
     best_t = hit ? t : best_t;
     best_uv.x = hit ? uv.x : best_uv.x;
     best_uv.y = hit ? uv.y : best_uv.y;

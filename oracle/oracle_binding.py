@@ -391,6 +391,24 @@ def light_probe(precision, scene_data, ref, ref_n, sxy=None, emitter=-1, point=N
                 value=out[:, 11:14], pdf_direct=out[:, 14], pdf_area=out[:, 15], p=out[:, 16:19], env_center=info[0:3], env_radius=info[3], cdf=info[4:])
 
 
+def ray_probe(precision, scene_data, o, d, tmin, tmax):
+    """The oracle's own shape loop (intersectShape over every shape, closest hit in [tmin, tmax]) ray by ray, in float (32) or
+    double (64) arithmetic, without the AABB clip and the epsilon scaling of rayIntersect -> shape (-1: none), t, its.p."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    o = f(o)
+    n = len(o)
+    rows = np.zeros((n, 8))
+    rows[:, 0:3], rows[:, 3:6], rows[:, 6], rows[:, 7] = o, f(d), f(tmin), f(tmax)
+    out = np.zeros((n, 5))
+    L = lib()
+    L.oracle_ray_probe.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    scene = scene_data.struct()
+    rc = L.oracle_ray_probe(precision, C.addressof(scene), n, rows.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise OracleError("ray_probe: " + ("precision must be 32 or 64" if rc == -1 else "the scene does not load"))
+    return dict(shape=out[:, 0].astype(np.int64), t=out[:, 1], p=out[:, 2:5])
+
+
 def _elementwise(name, precision, args, cols, *ints):
     args = [np.ascontiguousarray(a, dtype=np.float64) for a in args]
     n = len(args[0])

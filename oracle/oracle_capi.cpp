@@ -774,7 +774,46 @@ template <typename F> static int lightProbe(const drmlt_scene *s, int mode, int 
     return 0;
 }
 
+// The oracle's own shape loop, ray by ray, in float or double arithmetic: intersectShape over every shape, closest hit in
+// [mint, maxt] (the loop of rayIntersect). Neither the AABB clip nor the epsilon scaling of rayIntersect: both belong to the caller's
+// ray set-up. A row of `in` (RAY_PROBE_IN doubles): o 0-2, d 3-5, mint 6, maxt 7. A row of `out` (RAY_PROBE_COLS doubles): 0 the shape
+// or -1, 1 t, 2-4 its.p.
+enum { RAY_PROBE_IN = 8, RAY_PROBE_COLS = 5 };
+template <typename F> static int rayProbe(const drmlt_scene *s, uint32_t n, const double *in, double *out) {
+    Scene<F> scene;
+    if (!scene.load(*s).empty()) return -2;
+    for (uint32_t i = 0; i < n; ++i) {
+        const double *x = in + (size_t) RAY_PROBE_IN * i;
+        double *o = out + (size_t) RAY_PROBE_COLS * i;
+        Ray<F> ray;
+        ray.o = V3<F>((F) x[0], (F) x[1], (F) x[2]); ray.d = V3<F>((F) x[3], (F) x[4], (F) x[5]);
+        ray.mint = (F) x[6]; ray.maxt = (F) x[7];
+        F maxt = ray.maxt, bu = 0, bv = 0;
+        int best = -1;
+        for (size_t k = 0; k < scene.shapes.size(); ++k) {
+            F t, u, v;
+            if (scene.intersectShape(scene.shapes[k], ray, ray.mint, maxt, t, u, v)) { maxt = t; best = (int) k; bu = u; bv = v; }
+        }
+        o[0] = best; o[1] = o[2] = o[3] = o[4] = 0;
+        if (best >= 0) {
+            Intersection<F> its;
+            its.t = maxt;
+            scene.fillIntersection(ray, best, bu, bv, its);
+            o[1] = maxt; o[2] = its.p.x; o[3] = its.p.y; o[4] = its.p.z;
+        }
+    }
+    return 0;
+}
+
 extern "C" {
+
+int oracle_ray_probe(int precision, const drmlt_scene *scene, uint32_t n, const double *in, double *out) {
+    try {
+        if (precision == 32) return rayProbe<float>(scene, n, in, out);
+        if (precision == 64) return rayProbe<double>(scene, n, in, out);
+    } catch (const std::exception &) { return -2; }
+    return -1;
+}
 
 int oracle_light_probe(int precision, const drmlt_scene *scene, int mode, int emitter, uint32_t n, const double *in, double *out, double *info) {
     try {

@@ -1,5 +1,5 @@
 // CPU harness of csrc/scene_prep.h (tests/test_scene_prep.py): what drmlt_create prepares for one scene and configuration.
-//   scene_prep_harness scene=FILE [tables=FILE] key=value ... [DRMLT_X=value ...]
+//   scene_prep_harness scene=FILE [tables=FILE] [params=FILE] key=value ... [DRMLT_X=value ...]
 // scene: a file written by SceneData.save(); keys are the fields of drmlt_config (defaults: abi.make_config's); DRMLT_* arguments
 // are put into the environment before read_knobs(). Prints one JSON object: the refusal (or ""), the scalar fields of DParams, the
 // PlanInputs, bvh_depth, ovf_entries and the byte count of every table; the raw tables go to `tables`, one after the other, in
@@ -30,7 +30,7 @@ int main(int argc, char **argv) {
         {"kelemen_style_weights", &cfg.kelemen_style_weights, nullptr}, {"kelemen_style_mutation", &cfg.kelemen_style_mutation, nullptr},
         {"no_light_image", &cfg.no_light_image, nullptr}, {"timeout_s", &cfg.timeout_s, nullptr}, {"no_direct_sampling", &cfg.no_direct_sampling, nullptr},
         {"seed_rule", &cfg.seed_rule, nullptr}, {"work_units_rule", &cfg.work_units_rule, nullptr}};
-    std::string scene_path, tables_path;
+    std::string scene_path, tables_path, params_path;
     for (int i = 1; i < argc; ++i) {
         const char *eq = strchr(argv[i], '=');
         if (!eq) { fprintf(stderr, "bad argument %s\n", argv[i]); return 2; }
@@ -39,6 +39,7 @@ int main(int argc, char **argv) {
         if (key.rfind("DRMLT_", 0) == 0) { setenv(key.c_str(), v, 1); continue; }
         if (key == "scene") { scene_path = v; continue; }
         if (key == "tables") { tables_path = v; continue; }
+        if (key == "params") { params_path = v; continue; }
         bool known = false;
         for (const auto &f : fields)
             if (key == f.name) {
@@ -66,6 +67,12 @@ int main(int argc, char **argv) {
         for (const auto &t : tables)
             if (t.bytes && fwrite(t.p, t.bytes, 1, f) != 1) { fprintf(stderr, "short write to %s\n", tables_path.c_str()); return 2; }
         fclose(f);
+    }
+    // The raw DParams block (its pointers are null), for tests/native/ray_probe.hip. A file of its own, not an entry of "tables": the JSON's
+    // table list and the tables file are pinned by hashes in tests/test_scene_prep.py, which a further entry would change in every case.
+    if (!params_path.empty()) {
+        FILE *f = fopen(params_path.c_str(), "wb");
+        if (!f || fwrite(&S.P, sizeof S.P, 1, f) != 1 || fclose(f) != 0) { fprintf(stderr, "cannot write %s\n", params_path.c_str()); return 2; }
     }
 
     const DParams &P = S.P;

@@ -23,22 +23,7 @@ gpu = pytest.mark.gpu
 PATH8 = dict(max_depth=8, direct_samples=-1, luminance_samples=20000, work_units=N_CHAINS, sample_count=1, type="orbital")
 
 
-def one_box_room(scenes, res=32):
-    """cornell_c2's five diffuse walls and its quad light, nothing inside: one cuboid + one flat record"""
-    sd = scenes.SceneData("one_box_room")
-    white, red, green, black = sd.diffuse(0.725, 0.71, 0.68), sd.diffuse(0.63, 0.065, 0.05), sd.diffuse(0.14, 0.45, 0.091), sd.diffuse(0.0)
-    scenes._room(sd, white, red, green)
-    sd.rectangle(scenes.translate(0, 0.995, 0) @ scenes.rotate("x", 90) @ scenes.scale(0.25), black, radiance=(17.0, 12.0, 4.0))
-    sd.set_camera(scenes.lookat((0, 0, 3.9), (0, 0, 0), (0, 1, 0)), 39.3077, res, res, scenes.abi.FILTER_BOX, 0.5)
-    return sd
-
-
-def two_box_room(scenes, res=32):
-    """... and an axis-aligned diffuse box on its floor: two cuboids + one flat record"""
-    sd = one_box_room(scenes, res)
-    sd.name = "two_box_room"
-    sd.box(scenes.translate(0.2, -0.7, 0.1) @ scenes.scale(0.3, 0.3, 0.3), 0)
-    return sd
+from ray_probe import one_box_room, two_box_room  # noqa: E402  (the two rooms: one copy, shared with the ray probe)
 
 
 BUILT = {"one_box_room": one_box_room, "two_box_room": two_box_room}
