@@ -491,7 +491,10 @@ DEV BoxCand box_candidate(bool leave, float nx, float ny, float fx, float fy, fl
     c.p = a0 ? bxy.y : bxy.x; c.q = (a0 || a1) ? bzz : bxy.y;       // in-face coordinates: axis 0 (y, z), 1 (x, z), 2 (x, y)
     return c;
 }
-DEV void test_box(const BoxRec &G, f3 o, f3 d, float tmin, float &best_t, float2v &best_uv, int &best_ks) {
+// OPEN_KNOWN (trace_held): whether the cuboid lacks a face at all is a property of its three face words, and the caller knows it as a
+// wave-uniform flag. A closed cuboid has every entry face, `hole` is false on every lane, and neither the per-lane test nor its
+// ballot is computed: one scalar test in their place. An open cuboid runs the test and the block as they are.
+template <bool OPEN_KNOWN = false> DEV void test_box(const BoxRec &G, f3 o, f3 d, float tmin, float &best_t, float2v &best_uv, int &best_ks, bool open = true) {
     const uint32_t f0 = G.f0, f1 = G.f1, f2 = G.f2;
     const float ldz = fmaf(G.z0, d.x, fmaf(G.z1, d.y, G.z2 * d.z));
     const float loz = fmaf(G.z0, o.x, fmaf(G.z1, o.y, fmaf(G.z2, o.z, G.z3)));
@@ -510,10 +513,13 @@ DEV void test_box(const BoxRec &G, f3 o, f3 d, float tmin, float &best_t, float2
     BoxCand c = box_candidate(inside, nx, ny, fx, fy, tnear, tfar, lo, ld, loz, ldz, f0, f1, f2);
     // the scene has no face where the ray enters (the open side of a room seen from outside): the face it leaves through. Rare, and
     // then for many lanes at once: behind a wave-uniform test.
-    const bool hole = through && !inside && (c.hc & 1u) == 0u;
-    if (__ballot(hole)) {
-        const BoxCand c2 = box_candidate(true, nx, ny, fx, fy, tnear, tfar, lo, ld, loz, ldz, f0, f1, f2);
-        c.t = hole ? c2.t : c.t; c.p = hole ? c2.p : c.p; c.q = hole ? c2.q : c.q; c.hc = hole ? c2.hc : c.hc;
+    if (!OPEN_KNOWN || open) {
+        const bool hole = through && !inside && (c.hc & 1u) == 0u;
+        // (OPEN_KNOWN: the compare's mask is the ballot; __ballot goes through a 0 / 1 integer and a second compare)
+        if (OPEN_KNOWN ? __builtin_amdgcn_ballot_w64(hole) != 0ull : __ballot(hole) != 0ull) {
+            const BoxCand c2 = box_candidate(true, nx, ny, fx, fy, tnear, tfar, lo, ld, loz, ldz, f0, f1, f2);
+            c.t = hole ? c2.t : c.t; c.p = hole ? c2.p : c.p; c.q = hole ? c2.q : c.q; c.hc = hole ? c2.hc : c.hc;
+        }
     }
     const bool hit = through && (c.hc & 1u) != 0u && c.t >= tmin && c.t <= best_t;
     best_t = hit ? c.t : best_t;
@@ -611,39 +617,73 @@ template <bool TRI> DEV Hit trace_flat(const DParams &P, f3 o, f3 d, float tmin,
 }
 
 // trace_flat with the scene's records held by the caller, in vector registers across its loop (k_mutate_w2h, kernels.hip): up to
-// three cuboids and one flat record, tested in the streaming loops' order by the same routines on the same values, then the same
-// tail (a copy: as a shared routine it would have to leave every kernel that inlines trace_flat register for register as it is).
-// No memory is read. Slots beyond the scene's counts are skipped by wave-uniform tests.
+// three cuboids and one flat record, tested in the streaming loops' order by the same routines on the same values. No memory is
+// read. What the scene is comes as ONE wave-uniform word of flags (held_flags: the host-side layout of the records never changes
+// during a launch), each a scalar bit test here:
+//   HELD_BOX1, HELD_BOX2, HELD_FLAT   the slot is used. Slot 0 always is: launch_plan.h's w2_held_launch asks for n_box >= 1.
+//   HELD_OPEN0..2                     the cuboid lacks a face (test_box<true>: a closed one skips the `hole` test and its ballot)
+//   HELD_QUAD2                        some record's kind is PRIM_QUAD2 -- the flat record's or a cuboid face's. Only then can a hit
+//                                     need the sub-triangle arm of the tail; without the flag the arm is skipped by the wave.
+// The tail is trace_flat's on the same values, as selects: no lane-dependent branch and no saved exec mask (with `if`s it cost
+// three masks and two branches an iteration, and the PRIM_QUAD2 arm ran under an empty mask on scenes of rectangles).
 struct HeldScene {
     BoxRec box[3];
     FlatRec flat;
 };
-DEV Hit trace_held(const HeldScene &S, uint32_t n_box, uint32_t n_flat, f3 o, f3 d, float tmin, float tmax) {
+enum { HELD_BOX1 = 1, HELD_BOX2 = 2, HELD_FLAT = 4, HELD_OPEN0 = 8, HELD_OPEN1 = 16, HELD_OPEN2 = 32, HELD_QUAD2 = 64 };
+// (a face half-word: exists | code << 1 | kind << 4 | shade << 6)
+DEV bool held_half_missing(uint32_t half) { return (half & 1u) == 0u; }
+DEV bool held_half_quad2(uint32_t half) { return (half & 1u) != 0u && ((half >> 4) & 3u) == (uint32_t) PRIM_QUAD2; }
+DEV uint32_t held_box_flags(uint32_t f0, uint32_t f1, uint32_t f2, uint32_t open_bit) {
+    bool open = false, quad2 = false;
+    const uint32_t w[3] = {f0, f1, f2};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        open = open || held_half_missing(w[a] & 0xffffu) || held_half_missing(w[a] >> 16);
+        quad2 = quad2 || held_half_quad2(w[a] & 0xffffu) || held_half_quad2(w[a] >> 16);
+    }
+    return (open ? open_bit : 0u) | (quad2 ? (uint32_t) HELD_QUAD2 : 0u);
+}
+// the word of flags of a held scene with n_box cuboids and n_flat flat records (slots beyond the counts hold zeros and set nothing)
+DEV uint32_t held_flags(const HeldScene &S, uint32_t n_box, uint32_t n_flat) {
+    uint32_t flags = (n_box > 1u ? (uint32_t) HELD_BOX1 : 0u) | (n_box > 2u ? (uint32_t) HELD_BOX2 : 0u) | (n_flat > 0u ? (uint32_t) HELD_FLAT : 0u);
+#pragma unroll
+    for (uint32_t i = 0; i < 3u; ++i)
+        if (i < n_box) flags |= held_box_flags(S.box[i].f0, S.box[i].f1, S.box[i].f2, (uint32_t) HELD_OPEN0 << i);
+    if (n_flat > 0u && (S.flat.ks & 0xff) == PRIM_QUAD2) flags |= (uint32_t) HELD_QUAD2;
+    return flags;
+}
+DEV Hit trace_held(const HeldScene &S, uint32_t flags, f3 o, f3 d, float tmin, float tmax) {
     float best_t = tmax;
     float2v best_uv = {0.f, 0.f};
     int best_ks = -1;
-    if (n_box > 0u) test_box(S.box[0], o, d, tmin, best_t, best_uv, best_ks);
-    if (n_box > 1u) test_box(S.box[1], o, d, tmin, best_t, best_uv, best_ks);
-    if (n_box > 2u) test_box(S.box[2], o, d, tmin, best_t, best_uv, best_ks);
-    if (n_flat > 0u) test_flat<false>(S.flat, o, d, tmin, best_t, best_uv, best_ks);
+    test_box<true>(S.box[0], o, d, tmin, best_t, best_uv, best_ks, (flags & HELD_OPEN0) != 0u);
+    // (expected: the blocks stand in source order, each behind a guard that falls through when the slot is used)
+    if (__builtin_expect((flags & HELD_BOX1) != 0u, 1)) test_box<true>(S.box[1], o, d, tmin, best_t, best_uv, best_ks, (flags & HELD_OPEN1) != 0u);
+    if (__builtin_expect((flags & HELD_BOX2) != 0u, 1)) test_box<true>(S.box[2], o, d, tmin, best_t, best_uv, best_ks, (flags & HELD_OPEN2) != 0u);
+    if (__builtin_expect((flags & HELD_FLAT) != 0u, 1)) test_flat<false>(S.flat, o, d, tmin, best_t, best_uv, best_ks);
     Hit h{-1, best_t, best_uv.x, best_uv.y};
-    if (best_ks >= 0) {
-        if (best_ks & BOX_FACE_FLAG) { // a cuboid's face: its own (u, v) from the in-face coordinates, its own record
-            const uint32_t hc = (uint32_t) best_ks & 0xffffu;
-            const float uu = (hc & 2u) ? h.v : h.u, vv = (hc & 2u) ? h.u : h.v;
-            h.u = (hc & 4u) ? 1.f - uu : uu;
-            h.v = (hc & 8u) ? 1.f - vv : vv;
-            best_ks = (int) (((hc >> 4) & 3u) | ((hc >> 6) << 8));
-        }
-        h.prim = best_ks >> 8;
-        if ((best_ks & 0xff) == PRIM_QUAD2) { // sub-triangle (a,b,c) for v <= u, (a,c,d) otherwise; its own barycentrics
-            const bool second = h.v > h.u;
-            const float uu = second ? h.u : h.u - h.v, vv = second ? h.v - h.u : h.v;
-            h.prim += second ? 1 : 0;
-            h.u = uu; h.v = vv;
-        }
+    const bool any = best_ks >= 0;
+    const bool face = any && (best_ks & BOX_FACE_FLAG) != 0; // a cuboid's face: its own (u, v) from the in-face coordinates, its own record
+    const uint32_t hc = (uint32_t) best_ks & 0xffffu;
+    const float uu = (hc & 2u) ? h.v : h.u, vv = (hc & 2u) ? h.u : h.v;
+    const float fu = (hc & 4u) ? 1.f - uu : uu, fv = (hc & 8u) ? 1.f - vv : vv;
+    h.u = face ? fu : h.u;
+    h.v = face ? fv : h.v;
+    const int ks = face ? (int) (((hc >> 4) & 3u) | ((hc >> 6) << 8)) : best_ks;
+    h.prim = any ? ks >> 8 : -1;
+    if (flags & HELD_QUAD2) { // sub-triangle (a,b,c) for v <= u, (a,c,d) otherwise; its own barycentrics
+        const bool quad2 = any && (ks & 0xff) == PRIM_QUAD2;
+        const bool second = h.v > h.u;
+        const float qu = second ? h.u : h.u - h.v, qv = second ? h.v - h.u : h.v;
+        h.prim += (quad2 && second) ? 1 : 0;
+        h.u = quad2 ? qu : h.u; h.v = quad2 ? qv : h.v;
     }
     return h;
+}
+// ... by the scene's counts, for a caller that holds no word of flags (the ray probe of the tests: one call, the flags made on the spot)
+DEV Hit trace_held(const HeldScene &S, uint32_t n_box, uint32_t n_flat, f3 o, f3 d, float tmin, float tmax) {
+    return trace_held(S, held_flags(S, n_box, n_flat), o, d, tmin, tmax);
 }
 
 template <int FEAT = 15> DEV Hit trace(const DParams &P, f3 o, f3 d, float tmin, float tmax, bool any_hit) {
@@ -730,7 +770,15 @@ struct OneLightTables {
 // OneLightTables with the light's two records held by the caller, in vector registers across its loop (k_mutate_w2, compiled for two
 // waves per SIMD, has them to spare): no scalar load at the head of the step. The shape tag steers a wave-uniform branch of the
 // step and goes back to a scalar register (one v_readfirstlane); everything else is a VALU operand.
-struct HeldLightTables {
+// RECT (k_mutate_w2h): the light is a rectangle, known at compile time. Every scene that launch_plan.h's w2_held_launch accepts has one:
+// the launch is a one-light launch, so the light's shape is tagged PRIM_RECTANGLE or PRIM_TRIANGLE (device_types.h:
+// scene_has_one_light; a triangle with vertex normals is tagged PRIM_SMOOTH and is no such light). A triangle that emits is never
+// merged into a pair (scene_prep.h asks emitter < 0 of both halves), a cuboid takes rectangles and pairs only (scene_prep.h clears
+// `usable` for every other record before find_boxes), so the triangle stays a PRIM_TRIANGLE flat record,
+// has_plain_tri is set and w2_held_launch says no. The step then has
+// no triangle arm to compute and select away (path_step_diffuse: light_is_rectangle), and the tag goes to no scalar register.
+template <bool RECT> struct HeldLightTablesT {
+    static constexpr bool rectangle_light = RECT;
     LdsTables L;
     const DEmitter &E;
     const DShade &S;
@@ -738,9 +786,16 @@ struct HeldLightTables {
     DEV DBsdf bsdf(int i) const { return L.bsdf(i); }
     DEV DEmitter emitter(int) const { return E; }
     DEV float emitter_cdf_lo(int) const { return E.cdf_lo; }
-    DEV DShade emitter_shade(int, const DEmitter &) const { DShade s = S; s.bsdf = __builtin_amdgcn_readfirstlane(s.bsdf); return s; }
+    DEV DShade emitter_shade(int, const DEmitter &) const {
+        DShade s = S;
+        if constexpr (!RECT) s.bsdf = __builtin_amdgcn_readfirstlane(s.bsdf);
+        return s;
+    }
     DEV constexpr int n_emitters(const DParams &) const { return 1; }
 };
+typedef HeldLightTablesT<false> HeldLightTables;
+template <class T, class = void> struct light_is_rectangle : std::false_type {};
+template <class T> struct light_is_rectangle<T, std::void_t<decltype(T::rectangle_light)>> : std::integral_constant<bool, T::rectangle_light> {};
 // BSDF and emitter records in LDS, shading records in device memory: for kernels whose own rows leave less LDS than the shading table
 // needs (k_mutate_bdpt at two waves per SIMD: 19.25 KB of rows; the Cornell scene's 30 shading records are 1.9 KB, its four BSDFs and one
 // emitter 224 bytes)
@@ -1288,6 +1343,8 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
 // about 25 lanes step). When the block runs it is the block below, on every lane, with dn < 0 selecting as before; when it does
 // not, Li is what it was and dn, dr, lumPdf and Lm, which nothing else reads, are never computed -- not even as garbage.
 // (Commit b65b601 last carried a switch that compiled the unconditional block into k_mutate_w2h for an A/B run.)
+// light_is_rectangle<TablesT> (k_mutate_w2h's HeldLightTablesT<true>): the light point is the rectangle's; the triangle's form, a root
+// among its instructions, is not compiled in. Every other table type computes both and selects by the shape's tag, as before.
 template <class SamplerT, class TablesT, bool MASKED = true, bool RARE_EMITTER_HIT = false>
 DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, SamplerT &smp, const Hit &hit, bool shadow_clear,
                            ShadowRay &sr) {
@@ -1354,7 +1411,7 @@ DEV void path_step_diffuse(const DParams &P, const TablesT &T, PathState &ps, Sa
     const float sx = (sx0 - E.cdf_lo) / emPdf; // sampleReuse
     const DShade L = T.emitter_shade(ei, E);
     f3 lp;
-    if ((L.bsdf >> 24) == PRIM_RECTANGLE) lp = fma3(ld3(L.eu), sx, fma3(ld3(L.ev), sy, ld3(L.origin)));
+    if (light_is_rectangle<TablesT>::value || (L.bsdf >> 24) == PRIM_RECTANGLE) lp = fma3(ld3(L.eu), sx, fma3(ld3(L.ev), sy, ld3(L.origin)));
     else { const float a = sqrtf(fmaxf(0.f, 1.f - sx)); lp = fma3(ld3(L.eu), 1.f - a, fma3(ld3(L.ev), a * sy, ld3(L.origin))); }
     const f3 ln = ld3(L.n);
     const f3 dv = lp - p;

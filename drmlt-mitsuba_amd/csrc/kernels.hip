@@ -1018,7 +1018,11 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(
 // w2_held_launch; DRMLT_NO_W2_HELD keeps w2). Three more things are w2h's own, and nothing launches a mixed form, so the one parameter
 // selects them too: the decide is w2h_decide, by selects (w2: mh_decide and the twin's digest); the step runs its emitter-hit block only when
 // a bounce ray of the wave hit the light (RARE_EMITTER_HIT); and the proposals of both stages are filled in ONE flattened pass with one Philox
-// site (w2: two loops). stats[14..16] as w2, stats[17] counts w2h's waves. The loop stands in the kernel itself, not in a routine both call:
+// site (w2: two loops). And the iteration carries less around its arithmetic: the scene's shape is one held
+// word of flags, a scalar bit test per slot and per open cuboid (trace_held; the tail of the pass by selects); the step has no
+// triangle-light arm (HeldLightTablesT<true>); the hand-off's three copies stand ahead of its swaps and the two flags cross
+// the halves against whatever a register holds; the wave's ray test is the `or` of two compare masks.
+// stats[14..16] as w2, stats[17] counts w2h's waves. The loop stands in the kernel itself, not in a routine both call:
 // the tests of the build (tests/test_w2_flush_isa.py, test_w2h_isa.py, test_w2h_decide_isa.py, test_w2h_fill_isa.py) count by the kernel's lines.
 
 // the hand-off in one v_permlane32_swap per value: lane i < 32 keeps `keep`, lane 32 + i receives lane i's `give`
@@ -1122,7 +1126,7 @@ DEV void w2_flush(const DParams &P, const V4Lds &L, uint32_t &qn, uint32_t lane)
 // the scene's ray records of k_mutate_w2<true>; k_mutate_w2<false> holds none
 struct W2HeldScene {
     HeldScene S;
-    uint32_t counts; // n_box | n_flat_rec << 8
+    uint32_t flags; // HELD_* (device_path.h): which slots are used, which cuboids lack a face, whether any record is a triangle pair
 };
 struct W2StreamedScene {};
 // the twelve floats of a record's rows, pinned one by one, then as the vector pairs the tests read
@@ -1161,8 +1165,8 @@ DEV W2HeldScene w2_held_scene(const DParams &P) {
     if (n_flat > 0u) ks = P.prims_flat->kind_shade;
     hold_v(ks);
     F.ks = ks;
-    H.counts = n_box | (n_flat << 8);
-    hold_v(H.counts);
+    H.flags = held_flags(H.S, n_box, n_flat);
+    hold_v(H.flags);
     return H;
 }
 
@@ -1411,19 +1415,23 @@ template <bool HELD> __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_
         // one ray per lane: chain lanes their camera / bounce ray, helpers the shadow ray they were handed. When any lane has a ray
         // the whole wave runs the pass, whatever its lanes hold: registers in, registers out, and only lanes that traced read `h`
         // (a PH_FLUSH step reads hit.prim, a record's index or -1, and selects everything else away).
-        const bool tracing = helper ? helper_has_ray : ps.phase == PH_CLOSEST;
+        // (w2h forms the wave's test from the two compare masks: helper_has_ray is false on every chain lane, and a helper's phase
+        // is PH_IDLE from the prologue on, so `or` is the select)
+        const bool tracing = HELD ? (helper_has_ray || ps.phase == PH_CLOSEST) : (helper ? helper_has_ray : ps.phase == PH_CLOSEST);
         __builtin_amdgcn_s_setprio(0);
         if constexpr (HELD) {
-            if (__ballot(tracing)) {
-                const uint32_t counts = wave_uniform(scene.counts);
-                h = trace_held(scene.S, counts & 0xffu, counts >> 8, ps.o, ps.d, ps.tmin, ps.tmax);
-            }
+            if (__builtin_amdgcn_ballot_w64(tracing) != 0ull) h = trace_held(scene.S, wave_uniform(scene.flags), ps.o, ps.d, ps.tmin, ps.tmax);
         } else {
             SECTION_PARAMS(Pt);
             if (__ballot(tracing)) h = trace<0>(Pt, ps.o, ps.d, ps.tmin, ps.tmax, helper);
         }
         __builtin_amdgcn_s_setprio(3);
-        const unsigned occluded = from_upper_u((helper_has_ray && h.prim >= 0) ? 1u : 0u);
+        unsigned occluded;
+        if constexpr (HELD) { // (only chain lanes read it: the swap's other operand is whatever a register holds, not a copy of the flag)
+            unsigned any_v;
+            asm volatile("" : "=v"(any_v));
+            occluded = __builtin_amdgcn_permlane32_swap((helper_has_ray && h.prim >= 0) ? 1u : 0u, any_v, false, false)[1];
+        } else occluded = from_upper_u((helper_has_ray && h.prim >= 0) ? 1u : 0u);
         helper_has_ray = false;
         ShadowRay sr;
         asm volatile("" : "=v"(sr.d.x), "=v"(sr.d.y), "=v"(sr.d.z), "=v"(sr.tmin), "=v"(sr.tmax)); // whatever the registers hold: read under sr.valid only
@@ -1438,14 +1446,36 @@ template <bool HELD> __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_
                 Vs.eff_dim = Cs.eff_dim; Vs.rr_depth = Cs.rr_depth; Vs.max_depth = Cs.max_depth;
                 const LdsTables LT{Cs.shade_off, Cs.bsdf_off, 0u}; // (the emitter table is not read: HeldLightTables)
                 // (RARE_EMITTER_HIT = HELD: w2h runs the emitter-hit block only in an iteration in which a bounce ray hit the light)
-                path_step_diffuse<RowSampler, HeldLightTables, false, HELD>(Vs, HeldLightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
+                // (HeldLightTablesT<HELD>: every scene w2h is launched on has a rectangle light -- device_path.h has the argument)
+                typedef HeldLightTablesT<HELD> LightTables;
+                path_step_diffuse<RowSampler, LightTables, false, HELD>(Vs, LightTables{LT, Cs.light, Cs.light_shade}, ps, sms, h, occluded == 0u, sr);
             }
         }
         // hand the shadow ray of this vertex to the helper lane
+        if constexpr (HELD) {
+            // w2h: a swap writes both its operands, and the shadow ray starts where the bounce ray does -- one register, which needs a
+            // copy to be swapped with itself. The three copies stand here, ahead of the block of swaps, and the origin's swaps come last,
+            // behind the direction's and the interval's, so that no copy is followed at once by the swap that reads it (gfx950 then
+            // wants two idle states in between). The helper's flag is made a 0 / 1 word ahead of the copies for the same reason.
+            // (`kept`: what a chain lane keeps of the flag is never read, so the swap's other operand is whatever a register holds, no
+            // zero made for it -- named here, so that it is no register a swap has just written)
+            unsigned valid01 = sr.valid ? 1u : 0u, kept;
+            hold_v(valid01);
+            asm volatile("" : "=v"(kept));
+            float gx = sr.o.x, gy = sr.o.y, gz = sr.o.z;
+            hold_v(gx); hold_v(gy); hold_v(gz);
+            ps.d.x = lower_keeps(ps.d.x, sr.d.x); ps.d.y = lower_keeps(ps.d.y, sr.d.y); ps.d.z = lower_keeps(ps.d.z, sr.d.z);
+            ps.tmin = lower_keeps(ps.tmin, sr.tmin); ps.tmax = lower_keeps(ps.tmax, sr.tmax);
+            ps.o.x = lower_keeps(ps.o.x, gx); ps.o.y = lower_keeps(ps.o.y, gy); ps.o.z = lower_keeps(ps.o.z, gz);
+            // (`helper` selects the flag, a scalar `and` of two masks -- not `&&`, which would put the swap behind the helpers' exec mask)
+            const bool handed = lower_keeps_u(kept, valid01) != 0u;
+            helper_has_ray = helper & handed;
+        } else {
         ps.o.x = lower_keeps(ps.o.x, sr.o.x); ps.o.y = lower_keeps(ps.o.y, sr.o.y); ps.o.z = lower_keeps(ps.o.z, sr.o.z);
         ps.d.x = lower_keeps(ps.d.x, sr.d.x); ps.d.y = lower_keeps(ps.d.y, sr.d.y); ps.d.z = lower_keeps(ps.d.z, sr.d.z);
         ps.tmin = lower_keeps(ps.tmin, sr.tmin); ps.tmax = lower_keeps(ps.tmax, sr.tmax);
         helper_has_ray = lower_keeps_u(0u, sr.valid ? 1u : 0u) != 0u; // (a chain lane keeps the `false` set above)
+        }
     }
     // the epilogue of k_mutate_v4, on its own copy of the block; the last splat goes through this kernel's flush, called here by name
     // (the tests of the build find a flush's instructions by the kernel's line that called it)

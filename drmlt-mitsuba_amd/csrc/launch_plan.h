@@ -152,6 +152,10 @@ inline bool w2_launch(size_t lds, uint32_t grid, int cus) { return lds * 12u > C
 // k_mutate_w2h (kernels.hip) is k_mutate_w2 with the scene's ray records held in vector registers: room for three cuboids and one
 // flat record, tested without the plain-triangle arm. A scene without cuboids gains nothing from it (cornell_c1: three flat
 // records) and keeps streaming. The ONE place the condition is written down.
+// k_mutate_w2h's code leans on two things that follow from it (and from w2_launch's one-light condition): there is a cuboid in slot 0
+// (n_box >= 1: trace_held tests it without a guard), and the light is a RECTANGLE (no plain triangle among the flat records, and a
+// triangle that emits is always one: device_path.h, HeldLightTablesT -- the step is compiled without the triangle light's arm).
+// Whoever widens the condition takes both back.
 inline bool w2_held_launch(int n_box, int n_flat_rec, bool has_plain_tri) { return n_box >= 1 && n_box <= 3 && n_flat_rec >= 0 && n_flat_rec <= 1 && !has_plain_tri; }
 
 struct Family { int variant; bool tables_in_lds, rows_mem; };
