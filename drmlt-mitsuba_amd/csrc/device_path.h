@@ -437,6 +437,25 @@ struct FlatRec {
     int ks;
 };
 
+// The (u, v) rows of a record applied to a point and to a direction. BY_COMPONENT (trace_held): each component as its own chain of
+// fmaf / multiply in the nesting of the packed expression. A packed fused multiply-add is two independent fused multiply-adds, so
+// every component rounds as in the packed form (the unit is built with -ffp-contract=on: the packed expression fuses exactly where
+// the fmaf stands). Why: a v_pk_fma_f32 occupies the SIMD for two passes, and in k_mutate_w2h's loop, which is bound by VALU issue
+// at two waves per SIMD, the ray pass's 32 packed instructions cost more than the 50-odd plain ones that replace them (DESIGN
+// section 7a, r20: +0.5 %). The streaming loops keep the packed rows: their records arrive as aligned scalar register pairs.
+template <bool BY_COMPONENT> DEV float2v rows_at_point(float2v cx, float2v cy, float2v cz, float2v cw, f3 o) {
+    if constexpr (BY_COMPONENT) return float2v{fmaf(cx.x, o.x, fmaf(cy.x, o.y, fmaf(cz.x, o.z, cw.x))), fmaf(cx.y, o.x, fmaf(cy.y, o.y, fmaf(cz.y, o.z, cw.y)))};
+    else return cx * o.x + (cy * o.y + (cz * o.z + cw));
+}
+template <bool BY_COMPONENT> DEV float2v rows_at_direction(float2v cx, float2v cy, float2v cz, f3 d) {
+    if constexpr (BY_COMPONENT) return float2v{fmaf(cx.x, d.x, fmaf(cy.x, d.y, cz.x * d.z)), fmaf(cx.y, d.x, fmaf(cy.y, d.y, cz.y * d.z))};
+    else return cx * d.x + (cy * d.y + cz * d.z);
+}
+template <bool BY_COMPONENT> DEV float2v rows_along(float2v ld, float t, float2v lo) {
+    if constexpr (BY_COMPONENT) return float2v{fmaf(ld.x, t, lo.x), fmaf(ld.y, t, lo.y)};
+    else return ld * t + lo;
+}
+
 template <bool TRI> DEV void test_flat(const FlatRec &G, f3 o, f3 d, float tmin, float &best_t, float2v &best_uv, int &best_ks) {
     const float ldz = fmaf(G.z0, d.x, fmaf(G.z1, d.y, G.z2 * d.z));
     const float loz = fmaf(G.z0, o.x, fmaf(G.z1, o.y, fmaf(G.z2, o.z, G.z3)));
@@ -452,6 +471,21 @@ template <bool TRI> DEV void test_flat(const FlatRec &G, f3 o, f3 d, float tmin,
     // normal's span space, so a direction orthogonal to the normal's row and to one of u, v is not orthogonal to the other; that coordinate is
     // +-inf at t = +inf, and it or its 1 - x fails the test
     if (TRI) hit = hit && w >= 0.f;
+    best_t = hit ? t : best_t;
+    best_uv.x = hit ? uv.x : best_uv.x;
+    best_uv.y = hit ? uv.y : best_uv.y;
+    best_ks = hit ? G.ks : best_ks;
+}
+// test_flat<false> with its rows component by component (trace_held: no plain triangle among the records it is given)
+DEV void test_flat_held(const FlatRec &G, f3 o, f3 d, float tmin, float &best_t, float2v &best_uv, int &best_ks) {
+    const float ldz = fmaf(G.z0, d.x, fmaf(G.z1, d.y, G.z2 * d.z));
+    const float loz = fmaf(G.z0, o.x, fmaf(G.z1, o.y, fmaf(G.z2, o.z, G.z3)));
+    const float t = -loz * fast_rcp(ldz);
+    const float2v lo = rows_at_point<true>(G.cx, G.cy, G.cz, G.cw, o);
+    const float2v ld = rows_at_direction<true>(G.cx, G.cy, G.cz, d);
+    const float2v uv = rows_along<true>(ld, t, lo);
+    const float w = fminf(1.f - uv.x, 1.f - uv.y);
+    const bool hit = fminf(fminf(uv.x, uv.y), w) >= 0.f && t >= tmin && t <= best_t;
     best_t = hit ? t : best_t;
     best_uv.x = hit ? uv.x : best_uv.x;
     best_uv.y = hit ? uv.y : best_uv.y;
@@ -477,6 +511,7 @@ struct BoxRec {
 // value (arguments and result): through references the choice among the three face words compiles to a load through a selected
 // address, and the words then live in scratch memory.
 struct BoxCand { float t, p, q; uint32_t hc; };
+template <bool BY_COMPONENT = false>
 DEV BoxCand box_candidate(bool leave, float nx, float ny, float fx, float fy, float tnear, float tfar, float2v lo, float2v ld, float loz, float ldz,
                           uint32_t f0, uint32_t f1, uint32_t f2) {
     BoxCand c;
@@ -486,20 +521,30 @@ DEV BoxCand box_candidate(bool leave, float nx, float ny, float fx, float fy, fl
     const float lda = a0 ? ld.x : (a1 ? ld.y : ldz);
     const uint32_t w = a0 ? f0 : (a1 ? f1 : f2);
     c.hc = ((lda < 0.f) != leave) ? w >> 16 : w & 0xffffu;
-    const float2v bxy = ld * c.t + lo;
+    const float2v bxy = rows_along<BY_COMPONENT>(ld, c.t, lo);
     const float bzz = fmaf(ldz, c.t, loz);
     c.p = a0 ? bxy.y : bxy.x; c.q = (a0 || a1) ? bzz : bxy.y;       // in-face coordinates: axis 0 (y, z), 1 (x, z), 2 (x, y)
     return c;
 }
+// test_box<true>'s `hole` as ONE compare of a word that is pinned to a register: the ballot of a compare is the compare's mask, while of
+// an `and` of three masks the compiler makes a 0 / 1 integer and compares that again (two instructions a cuboid, and the pin keeps
+// it from folding the word back into the three masks).
+DEV bool held_hole(bool through_from_outside, uint32_t hc) {
+    uint32_t entry_exists = through_from_outside ? hc & 1u : 1u;
+    asm volatile("" : "+v"(entry_exists));
+    return entry_exists == 0u;
+}
 // OPEN_KNOWN (trace_held): whether the cuboid lacks a face at all is a property of its three face words, and the caller knows it as a
 // wave-uniform flag. A closed cuboid has every entry face, `hole` is false on every lane, and neither the per-lane test nor its
 // ballot is computed: one scalar test in their place. An open cuboid runs the test and the block as they are.
-template <bool OPEN_KNOWN = false> DEV void test_box(const BoxRec &G, f3 o, f3 d, float tmin, float &best_t, float2v &best_uv, int &best_ks, bool open = true) {
+// BY_COMPONENT (trace_held): the rows as scalar chains (rows_at_point).
+template <bool OPEN_KNOWN = false, bool BY_COMPONENT = false>
+DEV void test_box(const BoxRec &G, f3 o, f3 d, float tmin, float &best_t, float2v &best_uv, int &best_ks, bool open = true) {
     const uint32_t f0 = G.f0, f1 = G.f1, f2 = G.f2;
     const float ldz = fmaf(G.z0, d.x, fmaf(G.z1, d.y, G.z2 * d.z));
     const float loz = fmaf(G.z0, o.x, fmaf(G.z1, o.y, fmaf(G.z2, o.z, G.z3)));
-    const float2v lo = G.cx * o.x + (G.cy * o.y + (G.cz * o.z + G.cw));
-    const float2v ld = G.cx * d.x + (G.cy * d.y + G.cz * d.z);
+    const float2v lo = rows_at_point<BY_COMPONENT>(G.cx, G.cy, G.cz, G.cw, o);
+    const float2v ld = rows_at_direction<BY_COMPONENT>(G.cx, G.cy, G.cz, d);
     const float ix = fast_rcp(ld.x), iy = fast_rcp(ld.y), iz = fast_rcp(ldz);
     // slab distances. (1 - lo) * inv, not t0 + inv: a ray parallel to a slab (inv = inf) must see (-inf, +inf) inside it and
     // two equal infinities outside
@@ -510,14 +555,14 @@ template <bool OPEN_KNOWN = false> DEV void test_box(const BoxRec &G, f3 o, f3 d
     // selects on values (a flag that lives across a branch costs a v_cndmask and a v_cmp at every merge).
     const bool through = tnear <= tfar && tfar >= tmin && tnear <= best_t;
     const bool inside = !(tnear >= tmin);
-    BoxCand c = box_candidate(inside, nx, ny, fx, fy, tnear, tfar, lo, ld, loz, ldz, f0, f1, f2);
+    BoxCand c = box_candidate<BY_COMPONENT>(inside, nx, ny, fx, fy, tnear, tfar, lo, ld, loz, ldz, f0, f1, f2);
     // the scene has no face where the ray enters (the open side of a room seen from outside): the face it leaves through. Rare, and
     // then for many lanes at once: behind a wave-uniform test.
     if (!OPEN_KNOWN || open) {
-        const bool hole = through && !inside && (c.hc & 1u) == 0u;
-        // (OPEN_KNOWN: the compare's mask is the ballot; __ballot goes through a 0 / 1 integer and a second compare)
+        // (OPEN_KNOWN: held_hole makes `hole` ONE compare, whose mask is the ballot; __ballot goes through a 0 / 1 integer and a second compare)
+        const bool hole = OPEN_KNOWN ? held_hole(through && !inside, c.hc) : through && !inside && (c.hc & 1u) == 0u;
         if (OPEN_KNOWN ? __builtin_amdgcn_ballot_w64(hole) != 0ull : __ballot(hole) != 0ull) {
-            const BoxCand c2 = box_candidate(true, nx, ny, fx, fy, tnear, tfar, lo, ld, loz, ldz, f0, f1, f2);
+            const BoxCand c2 = box_candidate<BY_COMPONENT>(true, nx, ny, fx, fy, tnear, tfar, lo, ld, loz, ldz, f0, f1, f2);
             c.t = hole ? c2.t : c.t; c.p = hole ? c2.p : c.p; c.q = hole ? c2.q : c.q; c.hc = hole ? c2.hc : c.hc;
         }
     }
@@ -657,11 +702,11 @@ DEV Hit trace_held(const HeldScene &S, uint32_t flags, f3 o, f3 d, float tmin, f
     float best_t = tmax;
     float2v best_uv = {0.f, 0.f};
     int best_ks = -1;
-    test_box<true>(S.box[0], o, d, tmin, best_t, best_uv, best_ks, (flags & HELD_OPEN0) != 0u);
+    test_box<true, true>(S.box[0], o, d, tmin, best_t, best_uv, best_ks, (flags & HELD_OPEN0) != 0u);
     // (expected: the blocks stand in source order, each behind a guard that falls through when the slot is used)
-    if (__builtin_expect((flags & HELD_BOX1) != 0u, 1)) test_box<true>(S.box[1], o, d, tmin, best_t, best_uv, best_ks, (flags & HELD_OPEN1) != 0u);
-    if (__builtin_expect((flags & HELD_BOX2) != 0u, 1)) test_box<true>(S.box[2], o, d, tmin, best_t, best_uv, best_ks, (flags & HELD_OPEN2) != 0u);
-    if (__builtin_expect((flags & HELD_FLAT) != 0u, 1)) test_flat<false>(S.flat, o, d, tmin, best_t, best_uv, best_ks);
+    if (__builtin_expect((flags & HELD_BOX1) != 0u, 1)) test_box<true, true>(S.box[1], o, d, tmin, best_t, best_uv, best_ks, (flags & HELD_OPEN1) != 0u);
+    if (__builtin_expect((flags & HELD_BOX2) != 0u, 1)) test_box<true, true>(S.box[2], o, d, tmin, best_t, best_uv, best_ks, (flags & HELD_OPEN2) != 0u);
+    if (__builtin_expect((flags & HELD_FLAT) != 0u, 1)) test_flat_held(S.flat, o, d, tmin, best_t, best_uv, best_ks);
     Hit h{-1, best_t, best_uv.x, best_uv.y};
     const bool any = best_ks >= 0;
     const bool face = any && (best_ks & BOX_FACE_FLAG) != 0; // a cuboid's face: its own (u, v) from the in-face coordinates, its own record

@@ -1013,15 +1013,17 @@ __global__ void __launch_bounds__(CHAIN_BLOCK, V4_MIN_WAVES(BUILD)) k_mutate_v4(
 // most one flat record without plain triangles (bench.py's Cornell box: three cuboids and the light) has 58 dwords of records, which
 // never change during a launch. w2 streams them through two software-pipelined scalar loops in every iteration: the block's
 // pointers, then the records, counters, read-ahead and waits. w2h reads them once, in the prologue, pinned like W2Held, and the
-// pass is straight-line code that reads no memory at all (device_path.h: trace_held -- test_box and test_flat as they are, in the
-// loops' order, on the same values: the same chains bit for bit). launch_mutate runs it where the plan says so (launch_plan.h:
+// pass is straight-line code that reads no memory at all (device_path.h: trace_held -- test_box and test_flat's arithmetic, in the
+// loops' order, on the same values, the rows component by component where the loops use packed f32 (r20: each component rounds
+// alike): the same chains bit for bit). launch_mutate runs it where the plan says so (launch_plan.h:
 // w2_held_launch; DRMLT_NO_W2_HELD keeps w2). Three more things are w2h's own, and nothing launches a mixed form, so the one parameter
 // selects them too: the decide is w2h_decide, by selects (w2: mh_decide and the twin's digest); the step runs its emitter-hit block only when
 // a bounce ray of the wave hit the light (RARE_EMITTER_HIT); and the proposals of both stages are filled in ONE flattened pass with one Philox
 // site (w2: two loops). And the iteration carries less around its arithmetic: the scene's shape is one held
 // word of flags, a scalar bit test per slot and per open cuboid (trace_held; the tail of the pass by selects); the step has no
 // triangle-light arm (HeldLightTablesT<true>); the hand-off's three copies stand ahead of its swaps and the two flags cross
-// the halves against whatever a register holds; the wave's ray test is the `or` of two compare masks.
+// the halves against whatever a register holds; the wave's ray test is the `or` of two compare masks. And w2h expects its
+// bookkeeping branch to be skipped, so that the ray pass follows the loop head and the branch stands behind the hand-off (r20).
 // stats[14..16] as w2, stats[17] counts w2h's waves. The loop stands in the kernel itself, not in a routine both call:
 // the tests of the build (tests/test_w2_flush_isa.py, test_w2h_isa.py, test_w2h_decide_isa.py, test_w2h_fill_isa.py) count by the kernel's lines.
 
@@ -1238,7 +1240,11 @@ template <bool HELD> __global__ void __launch_bounds__(CHAIN_BLOCK, 2) k_mutate_
         const unsigned long long pmask = __ballot(parked);
         const unsigned long long rmask = __ballot(ps.phase != PH_DONE && ps.phase != PH_IDLE);
         if (!pmask && !rmask) break;
-        if (pmask && (__popcll(pmask) >= batch || !rmask)) {
+        const bool book = pmask && (__popcll(pmask) >= batch || !rmask);
+        // w2h expects the branch to be skipped -- about two iterations in three skip it --, and the compiler then lays the ray pass
+        // directly behind the loop head and the branch's thousand instructions behind the hand-off: the common iteration falls through.
+        // (k_mutate_w2 keeps the plain test, `if (pmask && (__popcll(pmask) >= batch || !rmask))`, and the layout it gives.)
+        if (HELD ? __builtin_expect(book, 0) : book) {
             // the branch's scalars: what steers wave-uniform branches, loop bounds and scalar addresses (importance, timid_after_large,
             // eff_dim, chain_done, waves_left) and the Philox keys -- one block for the whole branch
             DParams Pm{};
