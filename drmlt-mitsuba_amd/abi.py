@@ -114,6 +114,21 @@ def bdpt_layer_index(depth, s):
     return (depth - 1) * (depth + 4) // 2 + s if 1 <= depth <= BDPT_LAYERS_DEPTH_LIMIT and 0 <= s <= depth + 1 else -1
 
 
+PT_HIT, PT_DIRECT = 0, 1                      # drmlt_render_pt_layers' strategies: the BSDF-sampled ray's emitter, the light sample
+PT_LAYERS_DEPTH_LIMIT = 2 ** 30 - 1           # above it the products below leave 32 bits: the library answers -1
+PT_LAYERS_MAX_DEPTH = 24                      # drmlt_render_pt_layers refuses a context above it (a sample's terms wait in LDS)
+
+
+def pt_layer_count(max_depth):
+    """drmlt_pt_layer_count: layers (depth d, strategy) of a layered path-traced film, 1 <= d <= max_depth, two strategies each."""
+    return 2 * max_depth if 1 <= max_depth <= PT_LAYERS_DEPTH_LIMIT else -1
+
+
+def pt_layer_index(depth, strategy):
+    """drmlt_pt_layer_index: where layer (depth, strategy) lies among them (d edges, camera to emitter); -1 outside the ranges."""
+    return 2 * (depth - 1) + strategy if 1 <= depth <= PT_LAYERS_DEPTH_LIMIT and strategy in (PT_HIT, PT_DIRECT) else -1
+
+
 def make_config(**kw):
     """Defaults follow DRMLT's ctor (reference src/integrators/drmlt/drmlt.cpp:193-349)."""
     c = Config()

@@ -31,6 +31,7 @@ ABI_SYMBOLS = (
     "drmlt_node_destroy", "drmlt_bootstrap_luminances", "drmlt_seed_indices", "drmlt_comm_info", "drmlt_film_tile",
     "drmlt_render_direct", "drmlt_direct_split", "drmlt_node_render_direct", "drmlt_render_bdpt",
     "drmlt_bdpt_layer_count", "drmlt_bdpt_layer_index", "drmlt_render_bdpt_layers",
+    "drmlt_pt_layer_count", "drmlt_pt_layer_index", "drmlt_render_pt_layers",
     "drmlt_seed_device", "drmlt_seed_pool_device", "drmlt_node_seed_device", "drmlt_select_seeds_device", "drmlt_select_seeds_blocked",
 )
 
@@ -85,6 +86,9 @@ def load_library():
     L.drmlt_bdpt_layer_count.argtypes = [C.c_int32]
     L.drmlt_bdpt_layer_index.argtypes = [C.c_int32, C.c_int32]
     L.drmlt_render_bdpt_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_void_p]
+    L.drmlt_pt_layer_count.argtypes = [C.c_int32]
+    L.drmlt_pt_layer_index.argtypes = [C.c_int32, C.c_int32]
+    L.drmlt_render_pt_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_void_p]
     L.drmlt_chain_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.drmlt_last_error.restype = C.c_char_p
     L.drmlt_last_error.argtypes = [C.c_void_p]
@@ -344,6 +348,21 @@ class Context:
         mode = weighted if type(weighted) is int else (abi.LAYERS_WEIGHTED if weighted else abi.LAYERS_UNWEIGHTED)
         out = np.empty((abi.bdpt_layer_count(self.cfg.max_depth), self.height, self.width, 3), dtype=np.float32)
         self._chk(self.L.drmlt_render_bdpt_layers(self.h, spp, seed, mode, out.ctypes.data))
+        return out
+
+    def render_pt_layers(self, spp, seed=1, weighted=True):
+        """technique=path: render_pt(spp, seed)'s samples split by path length and strategy: (abi.pt_layer_count(max_depth), H, W, 3),
+        layer abi.pt_layer_index(d, strategy) holding the light of paths of d edges found by the BSDF-sampled ray (abi.PT_HIT) or by
+        the light sample (abi.PT_DIRECT). weighted: with their power-heuristic weights, the layers sum to render_pt's image;
+        without, each layer is its strategy used alone. `weighted` may also be one of abi.LAYERS_*: it is passed on as the mode.
+        A context of another technique is refused here, before the library is called."""
+        if self.cfg.technique != abi.TECH_PATH:
+            name = {v: k for k, v in abi.TECH_NAMES.items()}.get(self.cfg.technique, "?")
+            raise DrmltError(abi.E_INVALID, "render_pt_layers needs a context with technique=path, this one has technique=%s "
+                                            "(render_bdpt_layers splits the bidirectional estimate)" % name)
+        mode = weighted if type(weighted) is int else (abi.LAYERS_WEIGHTED if weighted else abi.LAYERS_UNWEIGHTED)
+        out = np.empty((max(abi.pt_layer_count(self.cfg.max_depth), 0), self.height, self.width, 3), dtype=np.float32)
+        self._chk(self.L.drmlt_render_pt_layers(self.h, spp, seed, mode, out.ctypes.data))
         return out
 
     def render_direct(self, direct_samples=None, hide_emitters=False, seed=1, rows=None):

@@ -1076,9 +1076,28 @@ DEV void path_begin(const DParams &P, PathState &ps, float v0, float v1) {
 // plain diffuse polygon scenes (the Cornell configs) carry none of the other code or its registers.
 // HAS_BEGIN = false: the caller starts every path with path_begin itself (k_mutate_v4: in its bookkeeping branch), the
 // step never sees PH_BEGIN and carries none of its code.
-template <bool DUAL, int FEAT, class SamplerT, class TablesT, bool HAS_BEGIN = true>
+// SinkT: told about every term the step adds to ps.Li, by the complete path's edge count d (camera to emitter) and its strategy.
+// ps.depth counts the surface vertices reached so far, and at each of the three places that add to Li it is the index of the LAST
+// surface vertex of the path: the light sample is taken there (parked, then added in PH_SHADOW with the depth unchanged), and the
+// emitter hit or the escape to the environment is seen before `ps.depth++` counts the hit. So d = ps.depth + 1 at all three.
+//   hit(d, term, weight)     the emitter found by the BSDF-sampled ray (area light or environment): Li += term * weight
+//   park(d, term, weight)    a light sample waits for its shadow ray: ps.nee = term * weight (weight 1 for a point light)
+//   shadow(d, clear)         that ray came back; clear: Li += ps.nee
+//   voided()                 the sample is invalid, Li = 0 and nothing is added after it
+// The default does nothing and costs nothing (every use is under `if constexpr (SinkT::enabled)`); k_render_pt_layers has the one
+// that does (kernels_layers_pt.hip). The dual-lane additions and path_step_diffuse have no sink.
+struct PathNoSink {
+    static constexpr bool enabled = false;
+    DEV void hit(int, f3, float) const {}
+    DEV void park(int, f3, float) const {}
+    DEV void shadow(int, bool) const {}
+    DEV void voided() const {}
+};
+
+template <bool DUAL, int FEAT, class SamplerT, class TablesT, bool HAS_BEGIN = true, class SinkT = PathNoSink>
 DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &smp, const Hit &hit, bool shadow_clear,
-                   ShadowRay &sr) {
+                   ShadowRay &sr, SinkT sink = SinkT()) {
+    static_assert(!SinkT::enabled || !DUAL, "the dual-lane additions have no sink");
     // (row samplers: the five components a step can draw are requested HERE, all together and ahead of the shading record's gather -- one
     // round trip beside it instead of `need` of them behind it; what the step does not draw is not used)
     float pre0 = 0.f, pre1 = 0.f, pre2 = 0.f, pre3 = 0.f, pre4 = 0.f;
@@ -1105,6 +1124,7 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
         need = 2; // film position, pathsampler.cpp:538-543
     } else if (!DUAL && ps.phase == PH_SHADOW) {
         if (hit.prim < 0) ps.Li = ps.Li + ps.nee; // unoccluded
+        if constexpr (SinkT::enabled) sink.shadow(ps.depth + 1, hit.prim < 0);
         B = T.bsdf(ps.bsdf);
     } else {
         if (hit.prim < 0) { // the ray left the scene
@@ -1118,6 +1138,7 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
                     const float lumPdf = ps.bdelta ? 0.f : INV_PI_F * fmaxf(0.f, dot3(ps.d, ps.n)) * (E.cdf_hi - E.cdf_lo);
                     float a = ps.bpdf * ps.bpdf, b = lumPdf * lumPdf;
                     ps.Li = fma3(ps.thr * ld3(E.radiance), a / (a + b), ps.Li);
+                    if constexpr (SinkT::enabled) sink.hit(ps.depth + 1, ps.thr * ld3(E.radiance), a / (a + b));
                 }
             }
             ps.phase = PH_DONE;
@@ -1163,6 +1184,7 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
                     }
                     float a = ps.bpdf * ps.bpdf, b = lumPdf * lumPdf;
                     ps.Li = fma3(ps.thr * ld3(E.radiance), a / (a + b), ps.Li);
+                    if constexpr (SinkT::enabled) sink.hit(ps.depth + 1, ps.thr * ld3(E.radiance), a / (a + b)); // (before ps.depth++ below)
                 }
             }
             ps.direct_on = true;                   // rRec.type = ERadianceNoEmission
@@ -1187,6 +1209,7 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
         if ((FEAT & 4) && is_zero3(n)) {
             B.type = 0;
             ps.Li = mk3(0.f, 0.f, 0.f);
+            if constexpr (SinkT::enabled) sink.voided();
         }
         ps.refn_zero = (FEAT & 2) && B.type == 1; // transmissive / two-sided: DirectSamplingRecord(its) zeroes refN
         // no light sample at a delta vertex, dielectric or smooth conductor (path.cpp:187, the ESmooth gate)
@@ -1282,6 +1305,7 @@ DEV void path_step(const DParams &P, const TablesT &T, PathState &ps, SamplerT &
                     f3 c = ps.thr * value * bsdfVal * (point ? 1.f : a / (a + b));
                     if (!is_zero3(c)) {
                         ps.nee = c;
+                        if constexpr (SinkT::enabled) sink.park(ps.depth + 1, ps.thr * value * bsdfVal, point ? 1.f : a / (a + b));
                         ps.nrays++;
                         if (DUAL) { // partner lane traces it while this lane traces the bounce ray
                             sr.o = p; sr.d = dd;

@@ -6,6 +6,7 @@
 #include "drmlt_ctx.h"
 #include "scene_prep.h"
 #include "bdpt_layers.h"
+#include "pt_layers.h"
 #include "seed_select.h"
 
 #include <hip/hip_runtime.h>
@@ -45,6 +46,8 @@ void launch_render_pt(const DParams &P, uint64_t n_samples, uint32_t stream, flo
 void launch_render_bdpt(const DParams &P, uint32_t n, float scale, size_t lds, hipStream_t st);
 // ... split by path length and strategy into a layered film (kernels_layers_bdpt.hip)
 void launch_layers_bdpt(const DParams &P, uint32_t n, float scale, float *layers, int unweighted, size_t lds, hipStream_t st);
+// technique=path's independent samples split by path length and strategy (kernels_layers_pt.hip)
+void launch_render_pt_layers(const DParams &P, uint32_t n, float scale, double *layers, int unweighted, hipStream_t st);
 // the direct-illumination pass (kernels_direct.hip)
 uint32_t direct_grid(const DirectJob &J, int width);
 void launch_render_direct(const DParams &P, const DirectJob &J, float *out, hipStream_t st);
@@ -987,6 +990,56 @@ int drmlt_render_bdpt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out_layers, layers.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DRMLT_OK;
+}
+
+int drmlt_pt_layer_count(int32_t max_depth) { return pt_layer_count(max_depth); }
+int drmlt_pt_layer_index(int32_t depth, int32_t strategy) { return pt_layer_index(depth, strategy); }
+
+// drmlt_render_pt's samples, term by term: what path_step adds to a sample's radiance goes into layer (d, strategy) of a layered
+// film, which is an allocation of this call. Like drmlt_render_pt it writes nothing of the context but the traversal's overflow
+// area (scratch of every launch): the film, b, chain states and counters stay as they were.
+int drmlt_render_pt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t mode, float *out_layers) {
+    if (!ctx || !out_layers) return DRMLT_E_INVALID;
+    if (spp == 0) return ctx->fail(DRMLT_E_INVALID, "render_pt_layers: spp is 0, a render takes at least one sample per pixel");
+    if (ctx->cfg.technique != DRMLT_TECH_PATH)
+        return ctx->fail(DRMLT_E_INVALID, "drmlt_render_pt_layers needs a context with technique=path, this one has technique=%s "
+                                          "(drmlt_render_bdpt_layers splits the bidirectional estimate)",
+                         ctx->cfg.technique == DRMLT_TECH_BDPT ? "bdpt" : ctx->cfg.technique == DRMLT_TECH_MMLT ? "mmlt" : "?");
+    if (mode != DRMLT_LAYERS_WEIGHTED && mode != DRMLT_LAYERS_UNWEIGHTED)
+        return ctx->fail(DRMLT_E_INVALID, "render_pt_layers: unknown mode %d (DRMLT_LAYERS_WEIGHTED = %d, DRMLT_LAYERS_UNWEIGHTED = %d)",
+                         (int) mode, (int) DRMLT_LAYERS_WEIGHTED, (int) DRMLT_LAYERS_UNWEIGHTED);
+    DParams P = ctx->P;
+    if (P.max_depth < 1 || P.max_depth > PT_LAYERS_MAX_DEPTH)
+        return ctx->fail(DRMLT_E_INVALID, "render_pt_layers: maxDepth %d: the layers need a path length bounded by 1 <= maxDepth <= %d, "
+                                          "technique=bdpt's bound (a sample's terms are held in LDS until it ends)", P.max_depth, PT_LAYERS_MAX_DEPTH);
+    const uint64_t n = (uint64_t) spp * (uint64_t) P.width * (uint64_t) P.height;
+    if (n >= (1ull << 32))
+        return ctx->fail(DRMLT_E_INVALID, "render_pt_layers: %u spp on %d x %d pixels are %llu samples, the sample address has 32 bits: "
+                                          "average several calls with different seeds", spp, P.width, P.height, (unsigned long long) n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf layers;
+    // the layered film is fp64 on the device and rounded to fp32 here, layer by layer (kernels_layers_pt.hip: pt_layer_put)
+    const size_t layer_floats = (size_t) P.width * P.height * 3, n_layers = (size_t) pt_layer_count(P.max_depth);
+    const size_t bytes = n_layers * layer_floats * sizeof(double);
+    if (layers.alloc(bytes) != hipSuccess) {
+        (void) hipGetLastError(); // (the failed allocation is reported here, not by the next call that asks for the last error)
+        return ctx->fail(DRMLT_E_DEVICE, "render_pt_layers: cannot allocate the layered film, %llu bytes (%d layers of %d x %d pixels in fp64)",
+                         (unsigned long long) bytes, pt_layer_count(P.max_depth), P.width, P.height);
+    }
+    HIP_TRY(ctx, hipMemsetAsync(layers.p, 0, bytes, ctx->stream));
+    P.film = nullptr; // nothing here writes a film but the kernel's own put
+    P.key0 = (uint32_t) seed; P.key1 = (uint32_t) (seed >> 32);
+    HIP_TRY(ctx, ensure_overflow(ctx, P, (size_t) 16384 * 64)); // the grid's lanes, as drmlt_render_pt
+    launch_render_pt_layers(P, (uint32_t) n, 1.0f / (float) spp, layers.as<double>(), mode == DRMLT_LAYERS_UNWEIGHTED, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<double> one(layer_floats);
+    for (size_t l = 0; l < n_layers; ++l) {
+        HIP_TRY(ctx, hipMemcpyAsync(one.data(), layers.as<double>() + l * layer_floats, layer_floats * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float *const dst = out_layers + l * layer_floats;
+        for (size_t i = 0; i < layer_floats; ++i) dst[i] = (float) one[i];
+    }
     return DRMLT_OK;
 }
 

@@ -356,6 +356,38 @@ enum { DRMLT_LAYERS_WEIGHTED = 0, DRMLT_LAYERS_UNWEIGHTED = 1 };
 int drmlt_bdpt_layer_count(int32_t max_depth);
 int drmlt_bdpt_layer_index(int32_t depth, int32_t s);
 int drmlt_render_bdpt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t mode, float *out_layers);
+/* drmlt_render_pt's samples split by path length and strategy: the unidirectional estimator (MIPathTracer::Li,
+ * path.cpp) term by term. A layer is a pair (depth d, strategy): d the number of edges of the complete light path,
+ * camera to emitter -- drmlt_bdpt_layer_index's d -- and strategy the way the path found its emitter.
+ * DRMLT_PT_DIRECT: the light sample taken at a surface vertex, added once its shadow ray comes back clear
+ * (path.cpp:187-238). DRMLT_PT_HIT: the emitted light found by the BSDF-sampled ray, an area emitter it hits or
+ * the environment it escapes to (path.cpp:253-285). drmlt_pt_layer_index(d, strategy) = 2 (d - 1) + strategy,
+ * drmlt_pt_layer_count(D) = 2 D; both are plain arithmetic, need no device and give -1 outside 1 <= d (D) and
+ * strategy in {0, 1} (and above 2^30 - 1, where the products would leave 32 bits). The two d = 1 layers exist for regular indexing and stay zero: technique=path adds no emitted
+ * light on camera rays, and a light sample needs a surface vertex first.
+ * Depth: the path machine's counter (PathState::depth, the number of surface vertices reached, 1 at the camera
+ * ray's hit) is the index of the path's LAST surface vertex at each of the three places that add light -- the light
+ * sample is taken there and its shadow ray leaves the counter alone; the emitter hit and the escape to the
+ * environment are seen before the hit is counted -- so d = depth + 1 at all three.
+ * out_layers: count(max_depth)*H*W*3 floats, layer after layer. Sample i of the spp*W*H samples reads exactly the
+ * random numbers of sample i of drmlt_render_pt(ctx, spp, seed, ...): same sampler addressing, scale 1/spp, film
+ * position, reconstruction filter and context options (max_depth, rr_depth, direct_samples and what it excludes).
+ * DRMLT_LAYERS_WEIGHTED: each term as it is added to the sample's radiance; the layers sum to drmlt_render_pt's
+ * image. DRMLT_LAYERS_UNWEIGHTED: the term without its power-heuristic factor -- the hit without a/(a + b), the
+ * light sample without its miWeight -- so that a layer is its strategy used alone. Where the weight is 1 by
+ * construction (a point light's sample, a hit after a delta vertex) both modes give the same bits. A sample the
+ * estimator voids (a vertex normal without direction) is in no layer, as it is not in drmlt_render_pt's image.
+ * max_depth must lie in 1 .. 24, technique=bdpt's bound: a sample's terms are held on chip until the sample ends.
+ * The layered film is a device allocation of the call (DRMLT_E_DEVICE with the byte count if it cannot be had); it
+ * is summed in fp64 and rounded to fp32 once, so that the order of the device's atomic adds does not show in the
+ * result: two calls with the same arguments agree bit for bit but for sums within 1e-15 of a rounding boundary.
+ * Like drmlt_render_pt, which renders into a film of its own, the call leaves the context's film, b, chain states
+ * and counters as they were. DRMLT_E_INVALID: a technique other than path (named in the message), spp == 0,
+ * spp*W*H >= 2^32, an unknown mode, max_depth outside 1 .. 24, NULL pointers. */
+enum { DRMLT_PT_HIT = 0, DRMLT_PT_DIRECT = 1 };
+int drmlt_pt_layer_count(int32_t max_depth);
+int drmlt_pt_layer_index(int32_t depth, int32_t strategy);
+int drmlt_render_pt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t mode, float *out_layers);
 
 /* The direct-illumination image that develop adds when directSamples > 0
  * (BidirectionalUtils::renderDirectComponent, src/libbidir/util.cpp:30-92, with
