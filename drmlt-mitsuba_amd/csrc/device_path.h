@@ -661,7 +661,7 @@ template <bool TRI> DEV Hit trace_flat(const DParams &P, f3 o, f3 d, float tmin,
     return h;
 }
 
-// trace_flat with the scene's records held by the caller, in vector registers across its loop (k_mutate_w2h, kernels.hip): up to
+// trace_flat with the scene's records held by the caller, in vector registers across its loop (k_mutate_w2h, kernels_v4.hip): up to
 // three cuboids and one flat record, tested in the streaming loops' order by the same routines on the same values. No memory is
 // read. What the scene is comes as ONE wave-uniform word of flags (held_flags: the host-side layout of the records never changes
 // during a launch), each a scalar bit test here:

@@ -1,5 +1,5 @@
 // Device-side data layout of the DRMLT hot path (gfx950). Plain structs shared by the
-// host-side C-ABI (drmlt_capi.cpp) and the kernels (kernels.hip).
+// host-side C-ABI (drmlt_capi.cpp) and the kernels (kernels*.hip).
 //
 // HBM layout (all fp32 unless noted), n = chains on this GPU, D = PSS dims kept per chain:
 //   x        [D][n]   current PSS state, SoA: lane-contiguous 256 B rows per dimension

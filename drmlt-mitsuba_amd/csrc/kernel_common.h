@@ -1,4 +1,4 @@
-// Helpers shared by the chain kernels of all techniques (kernels.hip, kernels_mmlt.hip, kernels_bdpt.hip): film splats,
+// Helpers shared by the chain kernels of all techniques (kernels.hip, kernels_v3.hip, kernels_v4.hip, kernels_mmlt.hip, kernels_bdpt.hip): film splats,
 // splat normalisation, wave reductions. The decision logic they share is device_mh.h.
 #pragma once
 #include "device_path.h"

@@ -12,7 +12,7 @@
 #include <cstdlib>
 #include <string>
 
-// ---- LDS layout constants and formulas (kernels.hip, kernels_mmlt.hip, kernels_bdpt.hip, kernels_pssmlt_bdpt.hip)
+// ---- LDS layout constants and formulas (kernels_v3.hip, kernels_v4.hip, kernels_mmlt.hip, kernels_bdpt.hip, kernels_pssmlt_bdpt.hip)
 constexpr uint32_t V4_STRIDE = 33u;   // row stride of the sampler rows: (row + chain) mod 32 banks serve per-chain AND per-dimension access patterns
 constexpr uint32_t V4_QCAP = 160u;    // splat queue entries: flushed when a bookkeeping branch (at most 2 x 32 new entries) might not fit
 constexpr uint32_t V4_QCAP_BVH = 100u; // BVH scenes: their kernel also keeps the traversal stack in LDS (6 KB); flushes are a negligible part of it
@@ -26,7 +26,7 @@ constexpr int bdpt_eval_lds_floats(int max_depth) { return (2 * (2 * max_depth +
 // dynamic LDS bytes per wave (+ the scene tables, when they are staged)
 inline size_t v3_lds_bytes(size_t D) { return (D + 2 * ((D + 3) & ~(size_t) 3)) * 32 * sizeof(float); }
 // (k_mutate_v4: three row groups of D4 = D rounded up to 4 rows each; the D4 - D rows this formula does not count are taken from
-// the queue rows, which are up to 20 entries shorter than `qcap` -- v4_layout, kernels.hip)
+// the queue rows, which are up to 20 entries shorter than `qcap` -- v4_layout, kernels_v4.hip)
 inline size_t v4_lds_bytes(size_t D, size_t qcap) { return ((D + 2 * ((D + 3) & ~(size_t) 3) + 4) * V4_STRIDE + 32 + 5 * qcap + 3) / 4 * 4 * sizeof(float); }
 inline size_t v5_lds_bytes(uint32_t D, uint32_t qcap, bool coin_rows) { return ((size_t) D * 64u + (coin_rows ? 4u * 64u : 0u) + 64u + 5u * qcap + 8u * V5_SLOTS + 2u * (V5_SLOTS / 4u)) * sizeof(float); }
 inline size_t mmlt_lds_bytes(int mmlt_S, int mmlt_E, int max_depth) { return ((size_t) mmlt_S + mmlt_E + 1 + 3 * ((size_t) max_depth + 3)) * 64 * sizeof(float); }
@@ -49,7 +49,7 @@ struct Knobs {
     size_t bdpt_lds_pad = 0;                 // DRMLT_BDPT_LDS_PAD: extra LDS bytes of every bdpt kernel (occupancy experiments)
     bool no_run_ahead = false;               // DRMLT_NO_RUN_AHEAD
     bool rule_generic = false;               // DRMLT_RULE_GENERIC: k_mutate_v4 runs its generic body whatever the rule (device_types.h: rule_is_orbital)
-    bool no_w2 = false;                      // DRMLT_NO_W2: the orbital one-light launches of V4_F0 stay on k_mutate_v4's twin (kernels.hip: k_mutate_w2)
+    bool no_w2 = false;                      // DRMLT_NO_W2: the orbital one-light launches of V4_F0 stay on k_mutate_v4's twin (kernels_v4.hip: k_mutate_w2)
     bool no_w2_held = false;                 // DRMLT_NO_W2_HELD: k_mutate_w2 keeps streaming its ray records where k_mutate_w2h would hold them in registers (w2_held_launch below)
     bool one_light_generic = false;          // DRMLT_ONE_LIGHT_GENERIC: k_mutate_v4 reads the light from the staged tables however many the scene has (device_types.h: scene_has_one_light)
     long long ahead_cap = -1;               // DRMLT_AHEAD_CAP: mutations a chain may run beyond the launch's target; -1 = min(8 slices, 8192)
@@ -142,14 +142,14 @@ inline bool path_mh(const PlanInputs &in) { return in.technique == DRMLT_TECH_PA
 // (The ray-pool kernel v5 keeps ONE proposal row group in LDS; on flat scenes it needs two of its 64-chain waves on a SIMD: from
 // 98 304 chains up it is the default -- Cornell: v5 2.15e9 at 131 072 chains, 1.11e9 at 65 536; v4 1.79e9 at 65 536, 1.55e9 at
 // 131 072. BASELINE's config 2 fixes 65 536 chains and therefore runs k_mutate_v4. With chains for more than two waves per SIMD
-// (from 163 840 per 256 CUs) its proposal rows move to device memory and it is built for three waves per SIMD: kernels.hip, ROWS_MEM.)
-// k_mutate_w2 (kernels.hip) is compiled for two waves per SIMD and spends the registers of a third on constants it would otherwise
+// (from 163 840 per 256 CUs) its proposal rows move to device memory and it is built for three waves per SIMD: kernels_v4.hip, ROWS_MEM.)
+// k_mutate_w2 (kernels_v4.hip) is compiled for two waves per SIMD and spends the registers of a third on constants it would otherwise
 // re-read. It may replace a launch that can never have a third wave on a SIMD, for one of two reasons: the workgroup's LDS
 // exceeds a twelfth of a compute unit's 160 KB (four SIMDs x three waves), or the grid has no more than two waves per SIMD
 // of the device. The ONE place the condition is written down.
 constexpr size_t CU_LDS_BYTES = 160u * 1024u;
 inline bool w2_launch(size_t lds, uint32_t grid, int cus) { return lds * 12u > CU_LDS_BYTES || (uint64_t) grid <= (uint64_t) cus * 4u * 2u; }
-// k_mutate_w2h (kernels.hip) is k_mutate_w2 with the scene's ray records held in vector registers: room for three cuboids and one
+// k_mutate_w2h (kernels_v4.hip) is k_mutate_w2 with the scene's ray records held in vector registers: room for three cuboids and one
 // flat record, tested without the plain-triangle arm. A scene without cuboids gains nothing from it (cornell_c1: three flat
 // records) and keeps streaming. The ONE place the condition is written down.
 // k_mutate_w2h's code leans on two things that follow from it (and from w2_launch's one-light condition): there is a cuboid in slot 0

@@ -32,8 +32,8 @@ def test_touching_a_header_rebuilds_its_users(built, header):
         units = _would_rebuild()
         assert units, "%s is included by no object's dependency file: an edit would rebuild nothing" % os.path.basename(header)
         if os.path.basename(header) in ("device_mh.h", "device_path.h", "device_math.h"):
-            # the ONE copy of the decision logic / path machine: all three kernel units depend on it
-            for u in ("kernels.hip", "kernels_mmlt.hip", "kernels_bdpt.hip"):
+            # the ONE copy of the decision logic / path machine: the kernel units of all three techniques depend on it
+            for u in ("kernels.hip", "kernels_v3.hip", "kernels_v4.hip", "kernels_mmlt.hip", "kernels_bdpt.hip"):
                 assert any(u in l for l in units), (u, units)
     finally:
         os.utime(header, ns=(st.st_atime_ns, st.st_mtime_ns))

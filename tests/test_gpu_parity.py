@@ -352,7 +352,7 @@ def test_chain_kernel_generations_run_the_same_chains(pkg, ob, kw, native_lib):
         results.append((ctx.chain_state(34), ctx.stats(), ctx.film()))
     (c0, u0), s0, f0 = results[0]
     for (c, u), s, f in results[1:]:
-        # states AND luminances are bit-equal: kernels.hip is compiled with -ffp-contract=on (contraction as the source is written,
+        # states AND luminances are bit-equal: the units of technique=path are compiled with -ffp-contract=on (contraction as the source is written,
         # not as each kernel's inlined copy of the path step happens to be optimised) -- round 3 had relaxed this to 2e-6
         assert np.array_equal(u, u0) and np.array_equal(c["luminance"], c0["luminance"])
         for k in ("first", "large", "bold", "second", "second_large", "second_bold", "overall"):

@@ -1,4 +1,4 @@
-"""k_mutate_v4's one-light builds (kernels.hip: V4_ONE_LIGHT_BUILD) read the scene's one emitter and its shape's shading record
+"""k_mutate_v4's one-light builds (kernels_v4.hip: V4_ONE_LIGHT_BUILD) read the scene's one emitter and its shape's shading record
 from the parameter block instead of the staged tables: launch_mutate runs them in place of V4_F0 / V4_F0_STAMPS when
 scene_has_one_light(P) holds (device_types.h). The records are byte copies and every expression of the step is the same source
 expression, so a context forced onto the generic build (DRMLT_ONE_LIGHT_GENERIC=1) and a default one must run the same chains, bit

@@ -1,4 +1,4 @@
-"""k_mutate_v4's orbital builds (kernels.hip: V4_ORBITAL_BUILD) have the transition rule compiled in: launch_mutate runs them in
+"""k_mutate_v4's orbital builds (kernels_v4.hip: V4_ORBITAL_BUILD) have the transition rule compiled in: launch_mutate runs them in
 place of the generic build when rule_is_orbital(P) holds (device_types.h). They only remove code the rule cannot reach, so a
 context forced onto the generic build (DRMLT_RULE_GENERIC=1) and a default one must run the same chains, bit for bit: states,
 f(u) of the current states, every counter of stats(). (stats().mutations is the device's sum of the per-chain counts of decided

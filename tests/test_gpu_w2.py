@@ -1,4 +1,4 @@
-"""k_mutate_w2 (kernels.hip) is k_mutate_v4's orbital one-light twin compiled for two waves per SIMD: launch_mutate runs it in
+"""k_mutate_w2 (kernels_v4.hip) is k_mutate_v4's orbital one-light twin compiled for two waves per SIMD: launch_mutate runs it in
 place of the twin on V4_F0 launches that cannot have a third wave on a SIMD (launch_plan.h: w2_launch; the 96- and 80-chain
 grids here are such launches on any device). Its constants wait in vector registers and a fill item draws one Philox block,
 but every floating-point expression is a header routine it shares with the

@@ -1,4 +1,4 @@
-"""k_mutate_w2's film flush under a TABULATED filter (kernels.hip: w2_flush stages P.filter_lut in the wave's list area and the
+"""k_mutate_w2's film flush under a TABULATED filter (kernels_v4.hip: w2_flush stages P.filter_lut in the wave's list area and the
 footprint loops read it from LDS; the box cases are those of tests/test_gpu_w2.py and tests/test_gpu_w2_step.py). A default
 context against one created under DRMLT_NO_W2=1 (k_mutate_v4, whose flush reads the table from device memory), on the shapes of
 tests/test_gpu_w2.py: a 32 x 32 film, 96 chains, cornell_c2 with a Gaussian filter of radius 2 -- up to 4 x 4 adds per channel

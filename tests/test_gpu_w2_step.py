@@ -1,6 +1,6 @@
 """k_mutate_w2's step writes the vertex, the bounce, ps.nee and the shadow ray on every lane that steps and selects only what
 a path that has ended is still read for (path_step_diffuse<.., MASKED = false>, device_path.h), and its shadow ray reaches the
-helper lanes in one v_permlane32_swap per value (lower_keeps, kernels.hip). When any lane has a ray the whole wave runs the ray
+helper lanes in one v_permlane32_swap per value (lower_keeps, kernels_v4.hip). When any lane has a ray the whole wave runs the ray
 pass, so a lane without one overwrites its hit with what a garbage ray finds. None of this changes a floating-point expression, so
 a default context and one created under DRMLT_NO_W2=1 (k_mutate_v4's twin, masked copy-backs and copied hand-off) must
 still run the same chains bit for bit: states, f(u) of the current states, every counter of stats() -- tests/test_gpu_w2.py's

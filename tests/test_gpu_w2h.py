@@ -1,4 +1,4 @@
-"""k_mutate_w2h (kernels.hip) is k_mutate_w2 with the scene's ray records -- up to three cuboids and one flat record -- read once
+"""k_mutate_w2h (kernels_v4.hip) is k_mutate_w2 with the scene's ray records -- up to three cuboids and one flat record -- read once
 and held in vector registers: its ray pass is trace_held (device_path.h), test_box and test_flat in the streaming loops' order
 on the same values, with no memory access. launch_mutate runs it where the plan allows (launch_plan.h: w2_held_launch).
 

@@ -1,4 +1,4 @@
-"""k_mutate_w2h's bookkeeping branch decides by selects (kernels.hip: w2h_decide) and its step runs the emitter-hit block only in
+"""k_mutate_w2h's bookkeeping branch decides by selects (kernels_v4.hip: w2h_decide) and its step runs the emitter-hit block only in
 an iteration in which a bounce ray of the wave hit the light (device_path.h: path_step_diffuse<.., RARE_EMITTER_HIT = true>).
 k_mutate_w2 and k_mutate_v4's twin keep the state machine with its arms (mh_decide) and the unconditional block, so the three
 contexts of tests/test_gpu_w2h.py -- default (held), DRMLT_NO_W2_HELD=1, DRMLT_NO_W2=1 -- compare the two forms: the same chains

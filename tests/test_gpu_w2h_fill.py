@@ -1,4 +1,4 @@
-"""k_mutate_w2h (k_mutate_w2<true>, kernels.hip) fills the proposal rows of the chains it has decided in ONE flattened pass: the
+"""k_mutate_w2h (k_mutate_w2<true>, kernels_v4.hip) fills the proposal rows of the chains it has decided in ONE flattened pass: the
 first-stage and coin items of the chains that start a mutation, and behind them the second-stage items of the chains whose first
 stage was rejected, one PAIR of a Philox block each, all drawn at one Philox site; a second-stage item's tail is
 row_fill_second_pair_drawn (device_sampler.h). k_mutate_w2 and k_mutate_v4's twin keep the two loops and RowSamplerT::fill_second.

@@ -1,6 +1,6 @@
 """k_mutate_w2h's loop iteration without its scaffolding: the ray pass's tail by selects and its slots behind scalar flag tests
 (device_path.h: trace_held, HELD_*), a closed cuboid that skips the `hole` test (test_box<true>), the step without the triangle
-light's arm (HeldLightTablesT<true>), the hand-off's copies ahead of its swaps (kernels.hip), the wave's ray test from two
+light's arm (HeldLightTablesT<true>), the hand-off's copies ahead of its swaps (kernels_v4.hip), the wave's ray test from two
 compare masks. None of it changes a floating-point expression
 or the order of one, so the three contexts of tests/test_gpu_w2h.py -- default (k_mutate_w2h), DRMLT_NO_W2_HELD=1 (k_mutate_w2,
 streaming) and DRMLT_NO_W2=1 (k_mutate_v4's twin) -- must still run the same chains BIT FOR BIT: the chain state rows, cur_*, and

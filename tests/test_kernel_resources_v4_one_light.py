@@ -1,4 +1,4 @@
-"""Resources of k_mutate_v4's one-light builds (kernels.hip: V4_ONE_LIGHT_BUILD), from the compiler's resource remarks of the build
+"""Resources of k_mutate_v4's one-light builds (kernels_v4.hip: V4_ONE_LIGHT_BUILD), from the compiler's resource remarks of the build
 (libdrmlt_amd.so.resources): each runs in place of V4_F0 / V4_F0_STAMPS under one of the two rules, on the grid and the LDS planned
 for that build, so it must not need more of anything that decides how many waves share a SIMD. The twins move the light's records
 from vector to scalar registers, so the vector registers are held to the replaced build's as well.
@@ -9,7 +9,7 @@ As measured on the commit that adds this file (replaced build -> twin: VGPRs, sp
     V4_F0_STAMPS          173 -> 143, 32 -> 26, 2 -> 3
     V4_F0_STAMPS orbital  169 -> 138, 22 -> 22, 2 -> 3
 The stamps twins count their events (iterations, branches, tracing lanes, the histogram) in 32 bits per wave where the builds they
-replace use 64 (kernels.hip: StampCount): with 64-bit counts the orbital stamps twin spilled 24 scalars against 22, whatever was
+replace use 64 (kernels_v4.hip: StampCount): with 64-bit counts the orbital stamps twin spilled 24 scalars against 22, whatever was
 done to the light's records or to the build counters."""
 import os
 import re

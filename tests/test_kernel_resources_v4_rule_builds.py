@@ -1,4 +1,4 @@
-"""Resources of k_mutate_v4's orbital builds (kernels.hip: V4_ORBITAL_BUILD), from the compiler's resource remarks of the build
+"""Resources of k_mutate_v4's orbital builds (kernels_v4.hip: V4_ORBITAL_BUILD), from the compiler's resource remarks of the build
 (libdrmlt_amd.so.resources): each runs in place of a generic build on the grid and the LDS planned for that one, so it must not
 need more of anything that decides how many waves share a SIMD."""
 import os

@@ -1,4 +1,4 @@
-"""Resources of k_mutate_w2 (kernels.hip), from the compiler's resource remarks of the build (libdrmlt_amd.so.resources). The kernel
+"""Resources of k_mutate_w2 (kernels_v4.hip), from the compiler's resource remarks of the build (libdrmlt_amd.so.resources). The kernel
 is declared for two waves per SIMD and runs only launches that cannot have a third (launch_plan.h: w2_launch): it may use the
 whole register file of two waves -- 256 registers per lane, vector and accumulator registers together -- but nothing may spill
 and nothing may sit in scratch memory. As measured on the commit that adds this file: 199 VGPRs, no AGPRs, no spilled scalar."""

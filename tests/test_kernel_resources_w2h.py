@@ -1,4 +1,4 @@
-"""Resources of k_mutate_w2h (kernels.hip), from the compiler's resource remarks of the build (libdrmlt_amd.so.resources). The kernel
+"""Resources of k_mutate_w2h (kernels_v4.hip), from the compiler's resource remarks of the build (libdrmlt_amd.so.resources). The kernel
 is k_mutate_w2 plus the scene's ray records in vector registers, 58 dwords and a count word: it is declared for two waves per SIMD
 and may use their whole register file -- 256 registers per lane, vector and accumulator registers together -- but nothing may
 spill and nothing may sit in scratch memory (a spilled record would be re-read from memory in the pass that holds it in order

@@ -1,4 +1,4 @@
-"""k_mutate_w2h with its select-only decide (kernels.hip: w2h_decide), from the compiler's resource remarks of the build. The decide
+"""k_mutate_w2h with its select-only decide (kernels_v4.hip: w2h_decide), from the compiler's resource remarks of the build. The decide
 is one long block with a dozen lane masks alive in scalar registers, and the kernel stands at the edge of its vector registers:
 what tests/test_kernel_resources_w2h.py asks, and no spilled SCALAR register either (a prototype of the decide spilled six, and
 a spilled scalar pair is a v_writelane / v_readlane pair in the loop or across it). As measured on the commit that adds this

@@ -2,6 +2,7 @@
 much LDS. tests/native/plan_harness.cpp runs derive_chains + plan_chains on PlanInputs and an environment of DRMLT_* knobs.
 The table was written from the selection as it stood before launch_plan.h (the derivation in drmlt_create, the launchers'
 if-ladders); the last rows are the named differences."""
+import glob
 import json
 import os
 import re
@@ -129,3 +130,22 @@ def test_knob_table_names_every_knob():
     table = "\n".join(line for line in doc.splitlines() if line.startswith("| `DRMLT_"))
     missing = sorted(k for k in knobs if "`" + k not in table)
     assert len(knobs) > 25 and not missing, missing
+
+
+def test_every_build_has_its_case_in_one_unit():
+    """Every enumerator of launch_plan.h's Build is a `case Build::X` of exactly one launcher, and the chain-kernel families of
+    technique=path keep to their units (k_mutate_v4 and k_mutate_v5 share one: DESIGN.md section 3k): a build lost between them would
+    only show as an abort on the device. Source text only."""
+    enum = re.search(r"enum class Build \{(.*?)\};", open(os.path.join(CSRC, "launch_plan.h")).read(), re.S).group(1)
+    builds = re.findall(r"\b[A-Z][A-Z0-9_]*\b", re.sub(r"//.*", "", enum))
+    assert len(builds) > 50 and len(set(builds)) == len(builds), builds
+    cases = {}  # enumerator -> [unit, ...], one entry per occurrence
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
+        for b in re.findall(r"\bcase Build::(\w+)\b", open(path).read()):
+            cases.setdefault(b, []).append(os.path.basename(path))
+    assert sorted(cases) == sorted(builds), set(cases) ^ set(builds)
+    assert all(len(units) == 1 for units in cases.values()), {b: u for b, u in cases.items() if len(u) != 1}
+    for prefixes, unit in ((("V3_",), "kernels_v3.hip"), (("V4_", "V5_"), "kernels_v4.hip")):
+        mine = [b for b in builds if b.startswith(prefixes)]
+        assert mine and all(cases[b] == [unit] for b in mine), (unit, {b: cases[b] for b in mine})
+        assert [b for b, u in cases.items() if u == [unit] and not b.startswith(prefixes)] == [], unit

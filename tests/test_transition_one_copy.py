@@ -32,5 +32,6 @@ def test_constant_is_used_by_one_routine(name):
 
 
 def test_kernels_call_no_transition_kernel():
-    text = open(os.path.join(CSRC, "kernels.hip")).read()
-    assert re.findall(r"\b(kelemen_sample|gaussian_sample|cos_rev)\s*\(", text) == []
+    for name in ("kernels.hip", "kernels_v3.hip", "kernels_v4.hip", "chain_path.h"):  # technique=path's units and what they share
+        text = open(os.path.join(CSRC, name)).read()
+        assert re.findall(r"\b(kelemen_sample|gaussian_sample|cos_rev)\s*\(", text) == [], name

@@ -1,5 +1,5 @@
 """k_mutate_w2h decides by selects and tests once per wave whether its step needs the emitter-hit block: a test of the BUILD, not
-of the GPU. kernels.hip is compiled to assembly once, as tests/test_w2h_isa.py does it (the unit's flags plus -S
+of the GPU. kernels_v4.hip is compiled to assembly once, as tests/test_w2h_isa.py does it (the unit's flags plus -S
 --cuda-device-only -gline-tables-only, about two minutes of CPU), and tools/isa_sections.py counts the instructions that the
 kernel's own source lines produced, with everything they inline.
 
@@ -21,7 +21,7 @@ import sys
 import pytest
 
 from test_w2h_isa import SYMBOL, TOOLS
-from test_w2h_isa import build  # noqa: F401  (the fixture: kernels.hip compiled to assembly, once for this module)
+from test_w2h_isa import build  # noqa: F401  (the fixture: kernels_v4.hip compiled to assembly, once per run)
 
 DECIDE_MAX = 244        # 324 with the arms, 214 in the prototype
 DECIDE_MASKS_WERE = 14  # saved exec masks of the section with the arms
@@ -29,7 +29,7 @@ STEP_BRANCHES = 3 + 1   # the step's three, and the wave's test of the emitter-h
 
 
 def sections(build, **ranges):  # noqa: F811
-    r = subprocess.run([sys.executable, os.path.join(TOOLS, "isa_sections.py"), build["asm"], SYMBOL, "kernels.hip",
+    r = subprocess.run([sys.executable, os.path.join(TOOLS, "isa_sections.py"), build["asm"], SYMBOL, build["file"],
                         *["%s=%d-%d" % (k, lo, hi) for k, (lo, hi) in ranges.items()]], check=True, capture_output=True, text=True)
     print(r.stdout)
     out = {}

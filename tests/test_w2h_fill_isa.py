@@ -1,4 +1,4 @@
-"""k_mutate_w2h fills the proposal rows in one flattened pass with one Philox site: a test of the BUILD, not of the GPU. kernels.hip
+"""k_mutate_w2h fills the proposal rows in one flattened pass with one Philox site: a test of the BUILD, not of the GPU. kernels_v4.hip
 is compiled to assembly once, as tests/test_w2h_isa.py does it (the unit's flags plus -S --cuda-device-only -gline-tables-only,
 about two minutes of CPU), and an instruction belongs to the kernel's own source line at which the chain of inlined calls that
 produced it starts (tools/isa_sections.py's rule).
@@ -11,7 +11,7 @@ row_fill_second_pair_drawn: its reads, ONE wait, then the rotation, then the sto
 import re
 
 from test_w2h_isa import SYMBOL
-from test_w2h_isa import build  # noqa: F401  (the fixture: kernels.hip compiled to assembly, once for this module)
+from test_w2h_isa import build  # noqa: F401  (the fixture: kernels_v4.hip compiled to assembly, once per run)
 from test_w2h_decide_isa import marker
 
 SYMBOL_STREAMED = "_Z11k_mutate_w2ILb0EEv7DParamsjj"  # k_mutate_w2<false>
@@ -21,7 +21,7 @@ PHILOX_MULTIPLIES = 20  # one philox4x32_10: ten rounds of two 32 x 32 -> 64 mul
 
 
 def by_line(build, symbol, lo, hi):  # noqa: F811
-    """[(source line of kernels.hip, instruction)] of `symbol` for the lines lo .. hi"""
+    """[(source line of kernels_v4.hip, instruction)] of `symbol` for the lines lo .. hi"""
     lines = build["text"].split("\n")
     st = next(i for i, l in enumerate(lines) if l.startswith(symbol + ":"))
     en = next(i for i in range(st, len(lines)) if "s_endpgm" in lines[i])
@@ -30,7 +30,7 @@ def by_line(build, symbol, lo, hi):  # noqa: F811
         if re.match(r"\s*\.loc\s", l):
             sites = re.findall(r"([\w.+-]+):(\d+):\d+", l.split(";", 1)[1] if ";" in l else "")
             if sites and int(sites[-1][1]) > 0:
-                cur = int(sites[-1][1]) if sites[-1][0] == "kernels.hip" else None
+                cur = int(sites[-1][1]) if sites[-1][0] == build["file"] else None
             continue
         t = l.split(";", 1)[0].strip()
         if not t or t.startswith((".", "//")) or t.endswith(":") or re.match(r"\.?\w+:", t):

@@ -1,6 +1,6 @@
-"""k_mutate_w2h's ray pass reads no memory, and its film flush is k_mutate_w2's: a test of the BUILD, not of the GPU. kernels.hip
-is compiled to assembly once, as tests/test_w2_flush_isa.py does it (the unit's flags plus -S --cuda-device-only
--gline-tables-only, about two minutes of CPU).
+"""k_mutate_w2h's ray pass reads no memory, and its film flush is k_mutate_w2's: a test of the BUILD, not of the GPU. kernels_v4.hip
+is compiled to assembly once, by tests/test_w2_flush_isa.py's `build` fixture (the unit's flags plus -S --cuda-device-only
+-gline-tables-only, about a minute of CPU), which this module hands on to the four that import it from here.
 
 The ray pass is the kernel's source lines between its s_setprio(0) and s_setprio(3). tools/isa_sections.py counts the
 instructions those lines produced, with everything they inline (trace_held, test_box, test_flat): none of them is a scalar
@@ -12,14 +12,10 @@ The flush: what tests/test_w2_flush_isa.py asserts for k_mutate_w2, by tools/isa
 import ast
 import os
 import re
-import shutil
 import subprocess
 import sys
 
-import pytest
-
-import bsdf_probe
-from test_w2_flush_isa import routine_lines
+from test_w2_flush_isa import build, routine_lines  # noqa: F401  (the fixture: kernels_v4.hip compiled to assembly, once per run)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "drmlt-mitsuba_amd", "csrc")
@@ -28,25 +24,9 @@ sys.path.insert(0, TOOLS)
 import isa_waits  # noqa: E402
 
 SYMBOL = "_Z11k_mutate_w2ILb1EEv7DParamsjj"  # k_mutate_w2<true>
-KERNEL_HEAD = " k_mutate_w2(DParams P,"     # the template's __global__ line in kernels.hip
 FLUSH_SITES = 3  # the bookkeeping branch's and the epilogue's two
 LOADS = ("s_load", "s_buffer_load", "flat_load", "global_load", "buffer_load", "scratch_load")
 RCPS = 3 * 3 + 1  # test_box: one per slab; test_flat: one
-
-
-@pytest.fixture(scope="module")
-def build(tmp_path_factory):
-    hipcc = bsdf_probe._make_var("HIPCC")[0]
-    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
-        pytest.skip("no hipcc")
-    out = str(tmp_path_factory.mktemp("w2h_isa") / "kernels.s")
-    r = subprocess.run([hipcc, "--offload-arch=" + bsdf_probe._make_var("ARCH")[0], *bsdf_probe.flags("kernels"), "-S", "--cuda-device-only",
-                        "-gline-tables-only", "-o", out, "kernels.hip"], cwd=CSRC, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    src = open(os.path.join(CSRC, "kernels.hip")).read().split("\n")
-    first = next(i for i, l in enumerate(src) if "__global__" in l and KERNEL_HEAD in l)
-    last = next(i for i in range(first, len(src)) if src[i] == "}")
-    return dict(asm=out, text=open(out).read(), src=src, kernel=(first + 1, last + 1))
 
 
 def test_ray_pass_by_source_lines(build):
@@ -54,7 +34,7 @@ def test_ray_pass_by_source_lines(build):
     lo = next(i for i in range(first, last) if "s_setprio(0)" in src[i]) + 1   # 1-based line of the marker
     hi = next(i for i in range(lo, last) if "s_setprio(3)" in src[i]) + 1
     assert any("trace_held(" in l for l in src[lo:hi - 1])
-    r = subprocess.run([sys.executable, os.path.join(TOOLS, "isa_sections.py"), build["asm"], SYMBOL, "kernels.hip", "rays=%d-%d" % (lo + 1, hi - 1)],
+    r = subprocess.run([sys.executable, os.path.join(TOOLS, "isa_sections.py"), build["asm"], SYMBOL, build["file"], "rays=%d-%d" % (lo + 1, hi - 1)],
                        check=True, capture_output=True, text=True)
     print(r.stdout)
     m = re.search(r"^rays\s+(\d+)\s+(\{.*\})$", r.stdout, re.M)
@@ -85,7 +65,7 @@ def test_flush_as_k_mutate_w2s(build):
     flush = routine_lines(src, "DEV void w2_flush(")
     sites = [i + 1 for i in range(first - 1, last) if re.search(r"\bw2_flush\(", src[i])]
     assert len(sites) == FLUSH_SITES, sites
-    res = isa_waits.scan(build["text"], SYMBOL, "kernels.hip", {"passes": (put[0], passes[1]), "staging": flush})
+    res = isa_waits.scan(build["text"], SYMBOL, build["file"], {"passes": (put[0], passes[1]), "staging": flush})
     c = res["passes"]
     print(dict((k, v) for k, v in c.items() if k != "where"), c["where"])
     assert c["vmem_atomic"] == 2 * FLUSH_SITES

@@ -1,4 +1,4 @@
-"""k_mutate_w2h's loop iteration carries less around its arithmetic: a test of the BUILD, not of the GPU. kernels.hip is compiled to
+"""k_mutate_w2h's loop iteration carries less around its arithmetic: a test of the BUILD, not of the GPU. kernels_v4.hip is compiled to
 assembly once, by tests/test_w2h_isa.py's fixture (the unit's flags plus -S --cuda-device-only -gline-tables-only, about two
 minutes of CPU), and an instruction belongs to the kernel's own source line at which the chain of inlined calls that produced it
 starts (tools/isa_sections.py's rule).
@@ -16,12 +16,12 @@ origin -- a swap writes both operands and the shadow ray starts where the bounce
 no s_nop between a copy and the swap that reads it. The step has
 no triangle-light arm (HeldLightTablesT<true>): its two roots are the distance to the light point and the cosine-hemisphere's.
 
-That the other 63 kernels of kernels.hip keep their machine code is tools/isa_same.py's business, parent against tree; it needs
+That the unit's other kernels keep their machine code is tools/isa_same.py's business, parent against tree; it needs
 the parent's tree and is run by hand."""
 import re
 
 from test_w2h_isa import SYMBOL
-from test_w2h_isa import build  # noqa: F401  (the fixture: kernels.hip compiled to assembly, once for this module)
+from test_w2h_isa import build  # noqa: F401  (the fixture: kernels_v4.hip compiled to assembly, once per run)
 from test_w2h_decide_isa import marker, sections
 from test_w2h_fill_isa import by_line
 

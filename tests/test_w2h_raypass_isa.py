@@ -1,5 +1,5 @@
 """k_mutate_w2h's ray pass holds no packed f32 instruction, and the loop's common iteration falls through: a test of the BUILD, not
-of the GPU. kernels.hip is compiled to assembly once, by tests/test_w2h_isa.py's fixture (the unit's flags plus -S
+of the GPU. kernels_v4.hip is compiled to assembly once, by tests/test_w2h_isa.py's fixture (the unit's flags plus -S
 --cuda-device-only -gline-tables-only, about two minutes of CPU), and an instruction belongs to the kernel's own source line at
 which the chain of inlined calls that produced it starts (tools/isa_sections.py's rule).
 
@@ -17,13 +17,13 @@ The layout: k_mutate_w2<true> expects its bookkeeping branch to be skipped, and 
 loop head and the branch behind the hand-off. In the assembly text the one s_setprio 2 (the branch opens with it) then stands
 behind s_setprio 0 and s_setprio 3 (the ray pass between them); on the parent it stood ahead of both.
 
-That the other 63 kernels of kernels.hip keep their machine code is tools/isa_same.py's business, parent against tree; it needs
+That the unit's other kernels keep their machine code is tools/isa_same.py's business, parent against tree; it needs
 the parent's tree and is run by hand."""
 import re
 import sys
 
 from test_w2h_isa import SYMBOL, TOOLS
-from test_w2h_isa import build  # noqa: F401  (the fixture: kernels.hip compiled to assembly, once for this module)
+from test_w2h_isa import build  # noqa: F401  (the fixture: kernels_v4.hip compiled to assembly, once per run)
 from test_w2h_decide_isa import sections
 from test_w2h_fill_isa import by_line
 from test_w2h_iter_isa import lines_of

@@ -3,7 +3,7 @@
 #   cd drmlt-mitsuba_amd/csrc && make -B OUT=../variants/libD.so DEVFLAGS="<the Makefile's DEVFLAGS> -mllvm -amdgpu-sched-strategy=max-ilp"
 # (drmlt-mitsuba_amd/variants/ is git-ignored; DRMLT_LIBRARY makes the binding load another build of the same ABI).
 # Run with VARIANTS="A D ..." here or in codegen_ab_bench.sh (config 2).
-# k_mutate_w2<HELD> (kernels.hip) has no source switches any more: each ingredient of the kernel was measured once against a
+# k_mutate_w2<HELD> (kernels_v4.hip) has no source switches any more: each ingredient of the kernel was measured once against a
 # build without it (profiles/), and commit b65b601 is the last that carries those nine -DW2_* / -DW2H_*
 # switches, should a measurement have to be repeated. w2h (k_mutate_w2<true>, the ray records held in registers) against w2
 # (k_mutate_w2<false>) needs no second build: DRMLT_NO_W2_HELD=1 is a run-time knob of the same library (launch_plan.h).

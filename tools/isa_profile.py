@@ -2,7 +2,7 @@
 
 In the lane-state-machine kernels every instruction of the main loop is issued for the wave on (nearly) every
 iteration, so code size per source region is a usable proxy for where the issue slots go.
-  hipcc --offload-arch=gfx950 -O3 ... -S --cuda-device-only -gline-tables-only -o /tmp/k.s kernels.hip
+  hipcc --offload-arch=gfx950 -O3 ... -S --cuda-device-only -gline-tables-only -o /tmp/k.s kernels_v4.hip
   python tools/isa_profile.py /tmp/k.s _Z11k_mutate_v3ILi0EEv7DParamsjj [bucket]
 """
 import collections

@@ -2,9 +2,12 @@
 kernel symbol of the first file: the instruction sequence from its label to s_endpgm, compared with the same symbol's of the second
 file. Comments, directives and .loc lines are dropped, and local labels (.LBB<n>_<m>) are renumbered by order of appearance, so that
 a kernel that moved within its file, or whose neighbours changed, still compares equal. A renamed kernel is given as old=new
-(mangled symbols). Per kernel: `identical`, or the first differing instruction and the two instruction counts.
+(mangled symbols); kernels that moved to other translation units are looked up in all the new files given. Per kernel: `identical`;
+`operands` -- equal once the two source operands of every commutative scalar instruction (s_and_b64 s[0:1], vcc, s[2:3]) are put in
+one order, the same machine operation; or `DIFFERS` with the first differing instruction and the two instruction counts.
   python tools/isa_same.py parent.s new.s _Z11k_mutate_w27DParamsjj=_Z11k_mutate_w2ILb0EEv7DParamsjj
-Exit status 1 if some kernel differs or is missing."""
+  python tools/isa_same.py parent/kernels.s kernels.s kernels_v3.s kernels_v4.s
+Exit status 1 if some kernel DIFFERS or is missing; `operands` is the same machine code and leaves it 0."""
 import re
 import sys
 
@@ -28,9 +31,20 @@ def kernels(path):
     return out
 
 
+COMMUTATIVE = re.compile(r'(s_(?:and|or|xor|nand|nor|xnor)_b(?:32|64)|s_(?:add|min|max)_[iu]32|s_mul_i32)\s+([^,]+), ([^,]+), ([^,]+)$')
+
+
+def ordered(body):
+    """the body with the source operands of its commutative scalar instructions sorted"""
+    return [COMMUTATIVE.sub(lambda m: '%s %s, %s, %s' % ((m.group(1), m.group(2)) + tuple(sorted(m.group(3, 4)))), t) for t in body]
+
+
 if __name__ == '__main__':
-    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
-    renamed = dict(a.split('=') for a in sys.argv[3:])
+    files = [a for a in sys.argv[1:] if '=' not in a]
+    old, new = kernels(files[0]), {}
+    for f in files[1:]:
+        new.update(kernels(f))
+    renamed = dict(a.split('=') for a in sys.argv[1:] if '=' in a)
     differ = 0
     for sym, a in old.items():
         b = new.get(renamed.get(sym, sym))
@@ -40,6 +54,8 @@ if __name__ == '__main__':
             print('MISSING    %s' % name)
         elif a == b:
             print('identical  %s (%d)' % (name, len(a)))
+        elif ordered(a) == ordered(b):
+            print('operands   %s (%d): %d commutative scalar instructions with their sources exchanged' % (name, len(a), sum(x != y for x, y in zip(a, b))))
         else:
             differ += 1
             i = next((i for i, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))

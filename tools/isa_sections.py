@@ -2,7 +2,7 @@
 -gline-tables-only): an instruction belongs to the line of the kernel's file at which the chain of inlined calls that produced it
 starts -- the last `file:line` of the .loc comment -- so a routine of a header counts where the kernel calls it. isa_region.py and
 isa_profile.py count by the innermost line instead: what a header routine costs, whoever calls it.
-  python tools/isa_sections.py /tmp/k.s <mangled kernel> kernels.hip bookkeeping=1049-1190 rays=1191-1198 step=1199-1240
+  python tools/isa_sections.py /tmp/k.s <mangled kernel> kernels_v4.hip bookkeeping=1049-1190 rays=1191-1198 step=1199-1240
 Instructions of the kernel outside every section (and those without a line) are reported as `other`.
 Per section it also reports `wait_vmcnt`, the s_waitcnt instructions that name vmcnt (loads, and on gfx9 no-return atomics and
 stores, count there: such a wait parks the wave until they have completed), and `vmem_load`, the vector-memory loads

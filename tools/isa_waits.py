@@ -4,7 +4,7 @@
 collects what the routine inlines as well, whichever kernel calls it; isa_sections.py reports the same two figures by the
 kernel's call sites alone. Per range: instructions, `wait_vmcnt` (s_waitcnt that name vmcnt: loads, and on gfx9 no-return
 atomics and stores, count there), `vmem_load` (flat_load*, global_load*), `vmem_atomic`, `lds` (ds_*).
-  python tools/isa_waits.py /tmp/k.s k_mutate_w2 kernels.hip passes=991-1015 staging=1016-1026
+  python tools/isa_waits.py /tmp/k.s k_mutate_w2 kernels_v4.hip passes=991-1015 staging=1016-1026
 The kernel is named by its source name or its mangled symbol. tests/test_w2_flush_isa.py imports scan()."""
 import collections
 import re

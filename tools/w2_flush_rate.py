@@ -1,7 +1,7 @@
 """Throughput of the chain kernel on bench.py's config 2 with a TABULATED reconstruction filter: the Cornell box 512 x 512,
 technique=path type=orbital, maxDepth 8, rrDepth 5, 65 536 chains, sampleCount 256 -- and a Gaussian filter of radius 2 in
 place of the box, so that a splat makes up to 4 x 4 atomic adds per channel through the filter table (k_mutate_w2: w2_flush,
-kernels.hip). bench.py has no such line. One warm-up call of one step, then --steps timed steps in one call, as bench.py runs
+kernels_v4.hip). bench.py has no such line. One warm-up call of one step, then --steps timed steps in one call, as bench.py runs
 them; one JSON line: mutations/s by the wall clock of the call, and Context.kernel_time() per launch (HIP events around the
 chain kernel's launches). A measurement, not a test:
     python tools/w2_flush_rate.py [--steps 5] [--filter gaussian|box] [--tag NAME]
