@@ -32,6 +32,7 @@ ABI_SYMBOLS = (
     "drmlt_render_direct", "drmlt_direct_split", "drmlt_node_render_direct", "drmlt_render_bdpt",
     "drmlt_bdpt_layer_count", "drmlt_bdpt_layer_index", "drmlt_render_bdpt_layers",
     "drmlt_pt_layer_count", "drmlt_pt_layer_index", "drmlt_render_pt_layers",
+    "drmlt_render_mmlt", "drmlt_render_mmlt_layers",
     "drmlt_seed_device", "drmlt_seed_pool_device", "drmlt_node_seed_device", "drmlt_select_seeds_device", "drmlt_select_seeds_blocked",
 )
 
@@ -89,6 +90,8 @@ def load_library():
     L.drmlt_pt_layer_count.argtypes = [C.c_int32]
     L.drmlt_pt_layer_index.argtypes = [C.c_int32, C.c_int32]
     L.drmlt_render_pt_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_void_p]
+    L.drmlt_render_mmlt.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
+    L.drmlt_render_mmlt_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_void_p]
     L.drmlt_chain_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     L.drmlt_last_error.restype = C.c_char_p
     L.drmlt_last_error.argtypes = [C.c_void_p]
@@ -363,6 +366,34 @@ class Context:
         mode = weighted if type(weighted) is int else (abi.LAYERS_WEIGHTED if weighted else abi.LAYERS_UNWEIGHTED)
         out = np.empty((max(abi.pt_layer_count(self.cfg.max_depth), 0), self.height, self.width, 3), dtype=np.float32)
         self._chk(self.L.drmlt_render_pt_layers(self.h, spp, seed, mode, out.ctypes.data))
+        return out
+
+    def _needs_mmlt(self, what, layered):
+        """The binding's own refusal of render_mmlt / render_mmlt_layers on a context of another technique, before the library is called."""
+        if self.cfg.technique != abi.TECH_MMLT:
+            name = {v: k for k, v in abi.TECH_NAMES.items()}.get(self.cfg.technique, "?")
+            other = ("render_bdpt" if self.cfg.technique == abi.TECH_BDPT else "render_pt") + ("_layers" if layered else "")
+            raise DrmltError(abi.E_INVALID, "%s needs a context with technique=mmlt, this one has technique=%s (%s is its reference)"
+                             % (what, name, other))
+
+    def render_mmlt(self, spp, seed=1):
+        """technique=mmlt: spp * W * H * max_depth independent samples of sampleSplats(EMMLT) -- spp per pixel PER DEPTH, sample i of
+        depth (i % max_depth) + 1 -- filtered into an (H, W, 3) image of develop's expectation, scale 1 / spp. Sample i is bootstrap
+        sample i of stream 0 under `seed` (bootstrap_luminances); the context's film and chains are left alone."""
+        self._needs_mmlt("render_mmlt", False)
+        out = np.empty((self.height, self.width, 3), dtype=np.float32)
+        self._chk(self.L.drmlt_render_mmlt(self.h, spp, seed, out.ctypes.data))
+        return out
+
+    def render_mmlt_layers(self, spp, seed=1, weighted=True):
+        """render_mmlt(spp, seed)'s samples split by path length and strategy: (abi.bdpt_layer_count(max_depth), H, W, 3), layer
+        abi.bdpt_layer_index(d, s) holding the samples of depth d that drew strategy s (t = d + 1 - s): render_bdpt_layers' index.
+        weighted: as the estimator returns them, the layers sum to render_mmlt's image; without the MIS weight, each layer is its
+        strategy used alone. `weighted` may also be one of abi.LAYERS_*: it is passed on as the mode."""
+        self._needs_mmlt("render_mmlt_layers", True)
+        mode = weighted if type(weighted) is int else (abi.LAYERS_WEIGHTED if weighted else abi.LAYERS_UNWEIGHTED)
+        out = np.empty((max(abi.bdpt_layer_count(self.cfg.max_depth), 0), self.height, self.width, 3), dtype=np.float32)
+        self._chk(self.L.drmlt_render_mmlt_layers(self.h, spp, seed, mode, out.ctypes.data))
         return out
 
     def render_direct(self, direct_samples=None, hide_emitters=False, seed=1, rows=None):

@@ -318,10 +318,18 @@ DEV float vert_pdf_sa(const DParams &P, const DBsdf &B, const BVert &v, f3 wi, f
 }
 
 // ------------------------------------------------------------------ the estimator
+// first LDS row behind a chain's state [sensor S | emitter E | direct]: where the MIS scratch of eval_mmlt starts
+DEV uint32_t mmlt_nx(const DParams &P) { return (uint32_t) (P.mmlt_S + P.mmlt_E + 1); }
+
+// eval_mmlt's sink, passed by value: told the sum of Path::miWeight's sweep (the splat carries its reciprocal) where a path reaches
+// the sweep. The default takes nothing and costs nothing: the chain, bootstrap, replay and evaluation kernels are built with it.
+// k_layers_mmlt (kernels_render_mmlt.hip) keeps the sum to undo the weight.
+struct MmltNoSink { DEV void mis_sum(double) const {} };
+
 // LDS rows used for the MIS sweep, per lane: pImp[NV], pRad[NV], gInv[NV] from row `mis_row`, NV = maxDepth + 3.
 // FEAT: as for trace() -- 15 with BVH traversal (its LDS stack, its registers), 7 without
-template <int FEAT = 15, class TablesT>
-DEV void eval_mmlt(const DParams &P, const TablesT &T, MSampler &smp, int depth, uint32_t mis_row, MmltResult &R) {
+template <int FEAT = 15, class TablesT, class SinkT = MmltNoSink>
+DEV void eval_mmlt(const DParams &P, const TablesT &T, MSampler &smp, int depth, uint32_t mis_row, MmltResult &R, SinkT sink = SinkT()) {
     const uint32_t lane = smp.lane;
     const uint32_t NV = (uint32_t) P.max_depth + 3u;
     auto pImp = [&](int j) -> float & { return lds_x[(mis_row + (uint32_t) j) * 64u + lane]; };
@@ -599,6 +607,7 @@ DEV void eval_mmlt(const DParams &P, const TablesT &T, MSampler &smp, int depth,
         if (((conn >> i) & 1u) && ((conn >> (i + 1)) & 1u) && (P.light_image || tPrime > 1)) weight += next * next;
         pdf = next;
     }
+    sink.mis_sum(weight);
     const float miw = 1.f / (float) weight;
     value = value * (geo * miw * (float) nStrats);
 

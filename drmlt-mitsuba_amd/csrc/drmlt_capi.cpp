@@ -32,6 +32,10 @@ void launch_bootstrap_mmlt(const DParams &P, uint32_t n, float *lum_out, size_t 
 void launch_init_chains_mmlt(const DParams &P, const uint32_t *seed_index, const float *seed_lum, size_t lds, hipStream_t st);
 void launch_mutate_mmlt(const ChainPlan &plan, const DParams &P, uint32_t n_mut, uint32_t mut_base, hipStream_t st);
 void launch_eval_paths_mmlt(const DParams &P, const float *u, uint32_t n, uint32_t dim, float *out8, size_t lds, hipStream_t st);
+// technique=mmlt's reference renders (kernels_render_mmlt.hip); `film` / `layers` are fp64
+uint32_t render_mmlt_grid(uint32_t n);
+void launch_render_mmlt(const DParams &P, uint32_t n, float scale, double *film, size_t lds, hipStream_t st);
+void launch_layers_mmlt(const DParams &P, uint32_t n, float scale, double *layers, int unweighted, size_t lds, hipStream_t st);
 void launch_regroup(const uint32_t *work, const int32_t *depth_or_null, uint32_t n, uint32_t n_mut, uint32_t md, uint32_t *order, uint32_t padded, uint32_t *scratch, hipStream_t st);
 size_t regroup_scratch_words(uint32_t n, uint32_t md);
 // technique=bdpt (kernels_bdpt.hip)
@@ -1019,7 +1023,7 @@ int drmlt_render_pt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t 
                                           "average several calls with different seeds", spp, P.width, P.height, (unsigned long long) n);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf layers;
-    // the layered film is fp64 on the device and rounded to fp32 here, layer by layer (kernels_layers_pt.hip: pt_layer_put)
+    // the layered film is fp64 on the device and rounded to fp32 here, layer by layer (layer_film.h: layer_put_f64)
     const size_t layer_floats = (size_t) P.width * P.height * 3, n_layers = (size_t) pt_layer_count(P.max_depth);
     const size_t bytes = n_layers * layer_floats * sizeof(double);
     if (layers.alloc(bytes) != hipSuccess) {
@@ -1041,6 +1045,67 @@ int drmlt_render_pt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t 
         for (size_t i = 0; i < layer_floats; ++i) dst[i] = (float) one[i];
     }
     return DRMLT_OK;
+}
+
+// Independent samples of sampleSplats(EMMLT) into an fp64 film, or into one film per (depth, strategy), which are allocations of
+// this call: sample i is bootstrap sample i of stream 0 under `seed`, depth (i % maxDepth) + 1, so every depth has spp * W * H
+// samples and the scale is 1 / spp (include/drmlt_abi.h has the derivation). Scratch is LDS and the traversal's overflow area
+// alone: the context's film, b, chain states and counters stay as they were. `layered`: drmlt_render_mmlt_layers, with `mode`.
+static int render_mmlt(drmlt_ctx *ctx, const char *name, uint32_t spp, uint64_t seed, bool layered, int32_t mode, float *out) {
+    if (!ctx || !out) return DRMLT_E_INVALID;
+    if (spp == 0) return ctx->fail(DRMLT_E_INVALID, "%s: spp is 0, a render takes at least one sample per pixel and depth", name);
+    if (ctx->cfg.technique != DRMLT_TECH_MMLT)
+        return ctx->fail(DRMLT_E_INVALID, "drmlt_%s needs a context with technique=mmlt, this one has technique=%s (%s is its reference)", name,
+                         ctx->cfg.technique == DRMLT_TECH_BDPT ? "bdpt" : ctx->cfg.technique == DRMLT_TECH_PATH ? "path" : "?",
+                         ctx->cfg.technique == DRMLT_TECH_BDPT ? (layered ? "drmlt_render_bdpt_layers" : "drmlt_render_bdpt")
+                                                               : (layered ? "drmlt_render_pt_layers" : "drmlt_render_pt"));
+    if (layered && mode != DRMLT_LAYERS_WEIGHTED && mode != DRMLT_LAYERS_UNWEIGHTED)
+        return ctx->fail(DRMLT_E_INVALID, "%s: unknown mode %d (DRMLT_LAYERS_WEIGHTED = %d, DRMLT_LAYERS_UNWEIGHTED = %d)", name,
+                         (int) mode, (int) DRMLT_LAYERS_WEIGHTED, (int) DRMLT_LAYERS_UNWEIGHTED);
+    DParams P = ctx->P;
+    const int n_layers = layered ? bdpt_layer_count(P.max_depth) : 1;
+    if (P.max_depth < 1 || n_layers < 1) return ctx->fail(DRMLT_E_INVALID, "%s: maxDepth %d has no layers", name, P.max_depth);
+    const uint64_t per_depth = (uint64_t) spp * (uint64_t) P.width * (uint64_t) P.height;
+    if (per_depth >= (1ull << 32) || per_depth * (uint64_t) P.max_depth >= (1ull << 32))
+        return ctx->fail(DRMLT_E_INVALID, "%s: %u spp on %d x %d pixels and %d depths are %llu x %d samples, the sample address has 32 bits: "
+                                          "average several calls with different seeds", name, spp, P.width, P.height, P.max_depth,
+                         (unsigned long long) per_depth, P.max_depth);
+    const uint32_t n = (uint32_t) (per_depth * (uint64_t) P.max_depth);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf films;
+    // the films are fp64 on the device and rounded to fp32 here, film by film (layer_film.h: layer_put_f64)
+    const size_t film_floats = (size_t) P.width * P.height * 3;
+    const size_t bytes = (size_t) n_layers * film_floats * sizeof(double);
+    if (films.alloc(bytes) != hipSuccess) {
+        (void) hipGetLastError(); // (the failed allocation is reported here, not by the next call that asks for the last error)
+        return ctx->fail(DRMLT_E_DEVICE, "%s: cannot allocate the film, %llu bytes (%d films of %d x %d pixels in fp64)", name,
+                         (unsigned long long) bytes, n_layers, P.width, P.height);
+    }
+    HIP_TRY(ctx, hipMemsetAsync(films.p, 0, bytes, ctx->stream));
+    P.film = nullptr; // nothing here writes a film but the kernel's own put
+    P.key0 = (uint32_t) seed; P.key1 = (uint32_t) (seed >> 32);
+    P.boot_stream = 0u;
+    P.importance = nullptr; // the image is of f itself
+    P.boot_weighted = 0;
+    HIP_TRY(ctx, ensure_overflow(ctx, P, (size_t) render_mmlt_grid(n) * 64)); // the grid's lanes
+    const float scale = 1.0f / (float) spp;
+    if (layered) launch_layers_mmlt(P, n, scale, films.as<double>(), mode == DRMLT_LAYERS_UNWEIGHTED, ctx->plan.aux_lds, ctx->stream);
+    else launch_render_mmlt(P, n, scale, films.as<double>(), ctx->plan.aux_lds, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<double> one(film_floats);
+    for (size_t l = 0; l < (size_t) n_layers; ++l) {
+        HIP_TRY(ctx, hipMemcpyAsync(one.data(), films.as<double>() + l * film_floats, film_floats * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        float *const dst = out + l * film_floats;
+        for (size_t i = 0; i < film_floats; ++i) dst[i] = (float) one[i];
+    }
+    return DRMLT_OK;
+}
+int drmlt_render_mmlt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb) {
+    return render_mmlt(ctx, "render_mmlt", spp, seed, false, DRMLT_LAYERS_WEIGHTED, out_rgb);
+}
+int drmlt_render_mmlt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t mode, float *out_layers) {
+    return render_mmlt(ctx, "render_mmlt_layers", spp, seed, true, mode, out_layers);
 }
 
 int drmlt_direct_split(int32_t direct_samples, int32_t *pixel_samples, int32_t *shading_samples) {

@@ -10,8 +10,6 @@
 #include "kernel_common.h"
 #include "launch_plan.h"
 
-DEV uint32_t mmlt_nx(const DParams &P) { return (uint32_t) (P.mmlt_S + P.mmlt_E + 1); }
-
 __global__ void __launch_bounds__(CHAIN_BLOCK) k_bootstrap_mmlt(DParams P, uint32_t n, float *lum_out) {
     const uint32_t lane = threadIdx.x;
     const uint32_t i = blockIdx.x * CHAIN_BLOCK + lane;

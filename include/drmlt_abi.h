@@ -388,6 +388,38 @@ enum { DRMLT_PT_HIT = 0, DRMLT_PT_DIRECT = 1 };
 int drmlt_pt_layer_count(int32_t max_depth);
 int drmlt_pt_layer_index(int32_t depth, int32_t strategy);
 int drmlt_render_pt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t mode, float *out_layers);
+/* Independent samples of the multiplexed integrand into a film: technique=mmlt's own equal-expectation reference.
+ * drmlt_render_bdpt differs from it in expectation: the multiplexed estimator returns nothing at depth 1
+ * (pathsampler.cpp:131), has no direct sampling (drmlt.cpp:229-231) and, without the light image, its own strategy set.
+ * The context must have technique=mmlt. A call takes n = spp*W*H*max_depth samples: spp is samples per pixel PER DEPTH.
+ * Sample i has depth (i % max_depth) + 1 (pathsampler.cpp:889) and reads exactly the random numbers of bootstrap sample i
+ * of stream 0 under `seed`, so its luminance is what drmlt_bootstrap_luminances(ctx, seed, 0, n, ...) reports at index i.
+ * Each sample is one PathSampler::sampleSplats(EMMLT) (pathsampler.cpp:84-320): one strategy (s, t) of its depth, drawn
+ * uniformly, its value times its MIS weight times the number of strategies. That one splat goes through the scene's
+ * reconstruction filter at its own position -- the sensor position for t >= 2, the light-image position for t = 1 -- with
+ * the validity test and footprint of the chains' splats.
+ * Scale 1/spp: every depth d has exactly spp*W*H samples, so the sum of the depth-d splats over spp*W*H is the Monte
+ * Carlo mean of the depth-d integrand over the film, and the image is the sum of these means over d. The reference
+ * reaches the same total from the other side: b is the mean over ALL bootstrap samples, of which only one in max_depth
+ * has a given depth, times max_depth (pathsampler.cpp:933; drmlt_capi.cpp, "As we split the path by corresponding
+ * depth"). The image's expectation is therefore that of drmlt_develop on this context.
+ * out_rgb: W*H*3 floats. The call follows the context's max_depth, rr_depth, no_light_image and direct_samples
+ * (>= 0: depth <= 2 is excluded, pathsampler.cpp:279) and ignores the importance map, acceptance_map,
+ * fix_emitter_path, type and algo. The film is a device allocation of the call (DRMLT_E_DEVICE with the byte count if
+ * it cannot be had), summed in fp64 and rounded to fp32 once: two calls with the same arguments agree bit for bit, as
+ * drmlt_render_pt_layers' do. The context's film, b, chain states and counters are left as they were.
+ * DRMLT_E_INVALID: another technique (named in the message, which points to drmlt_render_bdpt or drmlt_render_pt),
+ * spp == 0, n >= 2^32 (average several calls with different seeds), NULL pointers. */
+int drmlt_render_mmlt(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, float *out_rgb);
+/* The same samples split by path length and strategy. out_layers: drmlt_bdpt_layer_count(max_depth)*H*W*3 floats;
+ * layer drmlt_bdpt_layer_index(d, s) holds the samples of depth d that drew strategy s (t = d + 1 - s) -- deliberately
+ * the index of drmlt_render_bdpt_layers, so that the two stacks compare film by film. Layers no sample can reach stay
+ * zero: d = 1, t = 0, and t = 1 without the light image. DRMLT_LAYERS_WEIGHTED: the splat as sampleSplats(EMMLT) returns
+ * it (value x MIS weight x number of strategies); the layers sum to drmlt_render_mmlt's image. DRMLT_LAYERS_UNWEIGHTED:
+ * the same without the MIS weight; a layer is then strategy (s, t) used alone, equal in expectation to the unweighted
+ * layer of drmlt_render_bdpt_layers (without direct sampling). Scale, options, accumulation, what is left alone and
+ * what is refused are drmlt_render_mmlt's; an unknown mode is DRMLT_E_INVALID. */
+int drmlt_render_mmlt_layers(drmlt_ctx *ctx, uint32_t spp, uint64_t seed, int32_t mode, float *out_layers);
 
 /* The direct-illumination image that develop adds when directSamples > 0
  * (BidirectionalUtils::renderDirectComponent, src/libbidir/util.cpp:30-92, with
